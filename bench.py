@@ -7,7 +7,19 @@ One step = one pass of the hot path over the whole batch: rc_chunk_device (tile 
 every needed byte + chain kernel per stream), cut offsets left in HBM.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3i|3ii|3iii|4|5|harness]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (N > 1)
+
+A plain run does what the headline figure needs and no more: it sets up, warms up, times the
+K steps and prints the line (throughput, ms_per_step, the roofline of the timed steps' own
+kernel times).  `--full` adds everything that takes work of its own after the timed region:
+the parity check against the reference's cut lists, the same steps unpipelined, and the CPU
+baseline; without it those fields of the line are null.  `--dump-outputs DIR` writes what the
+last timed step left to its caller -- `counts.npy` (cuts per stream) and `cuts.npy` (the cut
+ends of the streams `cut_streams.npy` names, concatenated in that order; every stream unless
+that would pass DUMP_MAX_VALUES, then a fixed seeded sample of streams) -- as float64 (exact:
+offsets are far below 2^53); rank r > 0 of a multi-GPU run writes `<name>_rank<r>.npy`.  The
+inputs are the same synthetic streams on every run with the same arguments.
 
 `--gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset) starts the N ranks itself:
 a child `python -m torch.distributed.run --nproc-per-node N` over this same script, before
@@ -19,12 +31,12 @@ one-GPU rehearsal), and then the roofline is null (the ranks' HIP events time ea
 Ranks shard the work per stream (config 2: stream ids rank*1024 ..; config 4: stream i on
 GPU i mod 8) with no data-path collective: "scaling": "weak".  The process group is gloo and
 carries only the barriers, the max-over-ranks time and the parity flags -- never stream data.
-Rank 0 prints one JSON line.  Parity is checked in-run by EVERY rank against the reference's
-cut-list digests of that rank's own shard (tests/golden/ranks.json for ranks 0..7: config 2
-with key ff and the seeded key's first 128 streams, 3 (iii), 5; config4.json; the harness;
-3 (i) by its closed form; 3 (ii) for the stream lengths large.json / ranks.json hold); the
-line's flag is the AND over ranks, null when any rank has no fixture.  The CPU baseline runs
-on rank 0 over N x the per-GPU host-core share.
+Rank 0 prints one JSON line.  With --full, parity is checked in-run by EVERY rank against the
+reference's cut-list digests of that rank's own shard (tests/golden/ranks.json for ranks
+0..7: config 2 with key ff and the seeded key's first 128 streams, 3 (iii), 5; config4.json;
+the harness; 3 (i) by its closed form; 3 (ii) for the stream lengths large.json / ranks.json hold); the
+line's flag is the AND over ranks, null when any rank has no fixture.  The CPU baseline (--full)
+runs on rank 0 over N x the per-GPU host-core share.
 
 `--config harness` is the reference's own benchmark (Repository._benchmark_chunker,
 /root/reference/replicat/repository.py:1984-2008): 10 x 512,000,000 Random(0) bytes as one
@@ -76,11 +88,20 @@ def parse(argv=None):
     p.add_argument('--max-length', type=int, default=None, help='override the config\'s max')
     p.add_argument('--key', choices=['ff', 'seeded'], default='ff')
     p.add_argument('--cpu-streams', type=int, default=None,
-                   help='CPU-baseline sample in streams (default: all of config 2); 0 = skip')
+                   help='with --full: CPU-baseline sample in streams (default: all of config '
+                        '2); 0 = skip')
     p.add_argument('--cpu-procs', type=int, default=None,
                    help='CPU-baseline processes (default: the cores this process may use)')
     p.add_argument('--e2e', action='store_true', help='also time the host-resident path')
-    p.add_argument('--no-verify', action='store_true')
+    p.add_argument('--full', action='store_true',
+                   help='also do what takes work of its own after the timed steps: the parity '
+                        'check against the reference\'s cut lists (unless --no-verify), the same '
+                        'steps unpipelined, the CPU baseline (unless --cpu-streams 0)')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write the last step\'s outputs (cut counts and '
+                        'cut ends) as DIR/<name>.npy')
+    p.add_argument('--no-verify', action='store_true',
+                   help='with --full: skip the parity check')
     p.add_argument('--pipeline', choices=['on', 'off'], default='on',
                    help='on: steps are RC_PIPELINED calls -- the tile kernel on all but '
                         '--reserve-cus CUs, edge + chain kernels on those, so one step\'s chain '
@@ -274,7 +295,30 @@ def shard_ids(config, rank, n):
     return [rank * n + i for i in range(n)]
 
 
-def cut_digest(cuts_dev, counts_dev, caps):
+DUMP_MAX_VALUES = 6 << 20  # --dump-outputs: cut ends written at most (48 MiB as float64)
+DUMP_SEED = 20
+
+
+def dump_outputs(out_dir, ends, rank=0):
+    """--dump-outputs: the per-stream cut lists of the last timed step as float64 .npy files.
+    counts.npy holds every stream's count; cuts.npy the cut ends of the streams listed in
+    cut_streams.npy, concatenated in that order -- every stream in order when they fit in
+    DUMP_MAX_VALUES, else as many streams of a fixed seeded permutation as fit (a single list
+    longer than that is cut off there)."""
+    os.makedirs(out_dir, exist_ok=True)
+    counts = np.array([len(e) for e in ends], dtype=np.int64)
+    pick = np.arange(len(ends))
+    if counts.sum() > DUMP_MAX_VALUES:
+        perm = np.random.default_rng(DUMP_SEED).permutation(len(ends))
+        pick = perm[:max(1, int(np.searchsorted(np.cumsum(counts[perm]), DUMP_MAX_VALUES,
+                                                 side='right')))]
+    cuts = np.concatenate([np.asarray(ends[i], dtype=np.float64)[:DUMP_MAX_VALUES] for i in pick])
+    suffix = '' if rank == 0 else f'_rank{rank}'
+    for name, a in (('counts', counts), ('cut_streams', pick), ('cuts', cuts)):
+        np.save(os.path.join(out_dir, f'{name}{suffix}.npy'), np.asarray(a, dtype=np.float64))
+
+
+def cut_digest(cuts_dev, counts_dev, caps, digest=True):
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
     import golden_util as G
     from replicat_amd.chunker import check_counts
@@ -283,7 +327,7 @@ def cut_digest(cuts_dev, counts_dev, caps):
     check_counts(counts)  # a fail-safe stop (RC_COUNT_FAULT) or an overflow raises
     base = np.concatenate([[0], np.cumsum(caps)[:-1]]).astype(np.int64)
     ends = [cuts[b:b + c] for b, c in zip(base, counts)]
-    return G.cutlist_digest(ends), int(counts.sum()), ends
+    return G.cutlist_digest(ends) if digest else None, int(counts.sum()), ends
 
 
 def bytes_needed(max_length, lens, last):
@@ -942,21 +986,26 @@ def main(argv=None, backend=Backend):
     ms_per_step = elapsed * 1e3 / args.steps
     calls = max(calls, 1)
 
+    # the last timed step's cut lists on the host: only for the parity check (--full) or
+    # --dump-outputs; a plain run leaves them in HBM, as the timed path does
     parity, ends, scope = None, None, None
-    if not args.no_verify:
+    verify = args.full and not args.no_verify
+    if verify or args.dump_outputs:
         if long is not None:
             long.finish()
             ends = [np.asarray(long.ends, dtype=np.uint64)]
-            digest = _golden().cutlist_digest(ends)
+            digest = _golden().cutlist_digest(ends) if verify else None
         else:
-            digest, _, ends = cut_digest(cuts, counts, caps)
-        if not custom:
+            digest, _, ends = cut_digest(cuts, counts, caps, digest=verify)
+        if verify and not custom:
             parity, scope = check_parity(args, n, size, rank, long, edit, ends, digest)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ends, rank)
     LAST.update(device=be.index, ends=ends, parity=parity, rank=rank)
-    # the same step unpipelined (every kernel on one stream in sequence), after the timed
-    # region: what one call takes from its first kernel to its cuts
+    # --full: the same step unpipelined (every kernel on one stream in sequence), after the
+    # timed region: what one call takes from its first kernel to its cuts
     seq_ms = None
-    if pipelined and (long is None or world == 1):
+    if args.full and pipelined and (long is None or world == 1):
         seq = max(1, min(3, args.steps))
         step(False)
         be.synchronize()
@@ -991,8 +1040,9 @@ def main(argv=None, backend=Backend):
                              'no roofline')
         cpu = None
         # the CPU leg runs on rank 0 after the timed region, at every N (the other ranks wait
-        # at the final barrier); its sample is rank 0's own streams
-        if args.key == 'ff' and args.config == '2' and args.cpu_streams != 0:
+        # at the final barrier); its sample is rank 0's own streams (--full only)
+        cpu_leg = args.full and args.cpu_streams != 0
+        if cpu_leg and args.key == 'ff' and args.config == '2':
             procs, seen = cpu_share(world)
             procs = args.cpu_procs or procs
             sample = min(args.cpu_streams or n, n)
@@ -1016,7 +1066,7 @@ def main(argv=None, backend=Backend):
                                                            'sample')}
                 cpu['whole_mask']['matches_share'] = all(
                     list(whole_ends[i]) == list(cpu_ends[i]) for i in cpu_ends)
-        elif harness is not None and args.cpu_streams != 0:
+        elif cpu_leg and harness is not None:
             cpu, lengths = harness_cpu(harness, min_len, max_len)
             if cpu is not None and ends is not None:
                 cpu['matches_gpu'] = bool(np.array_equal(np.cumsum(lengths).astype(np.uint64),
@@ -1028,6 +1078,7 @@ def main(argv=None, backend=Backend):
             'n_gpus': world,
             'steps': args.steps,
             'warmup': args.warmup,
+            'full': args.full,
             'warmup_run': {'steps': warm_steps, 'ms': round(warm_s * 1e3, 1),
                            'rule': f'at least --warmup steps and {WARM_MS} ms of them'},
             'ms_per_step': round(ms_per_step, 3),

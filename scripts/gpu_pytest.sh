@@ -13,6 +13,6 @@ timeout -k 10 900 python -u -m pytest -x -v -p no:cacheprovider --timeout 300 --
 rc=$?; echo "pytest rc=$rc"; tail -n 3 $out/pytest.log
 [ $rc -eq 0 ] || exit $rc
 if [ $bench -eq 1 ]; then
-  timeout -k 10 400 python -u bench.py > $out/bench.log 2>&1 || { echo bench failed; tail -20 $out/bench.log; exit 4; }
+  timeout -k 10 400 python -u bench.py --full > $out/bench.log 2>&1 || { echo bench failed; tail -20 $out/bench.log; exit 4; }
   tail -n 1 $out/bench.log | cut -c1-300
 fi

@@ -54,8 +54,8 @@ def _run(argv, world=2):
 
 def test_config2_two_ranks():
     n, mib, steps = 3, 1, 2
-    out = _run(['--gpus', '2', '--config', '2', '--streams', str(n), '--stream-mib', str(mib), '--steps',
-                str(steps), '--warmup', '1', '--cpu-streams', '0', '--min-length', '2000',
+    out = _run(['--full', '--gpus', '2', '--config', '2', '--streams', str(n), '--stream-mib', str(mib),
+                '--steps', str(steps), '--warmup', '1', '--cpu-streams', '0', '--min-length', '2000',
                 '--max-length', '80000'])
     from oracle import oracle as o
     from replicat_amd import synth
@@ -84,8 +84,8 @@ def test_config3ii_split_over_two_ranks():
     """One stream split in two windows, chunked per rank, gathered and spliced: every rank ends
     with the whole true cut list of the stream."""
     mib = 4
-    out = _run(['--gpus', '2', '--config', '3ii', '--stream-mib', str(mib), '--steps', '1', '--warmup', '0',
-                '--cpu-streams', '0', '--min-length', '2000', '--max-length', '80000'])
+    out = _run(['--full', '--gpus', '2', '--config', '3ii', '--stream-mib', str(mib), '--steps', '1',
+                '--warmup', '0', '--cpu-streams', '0', '--min-length', '2000', '--max-length', '80000'])
     from oracle import oracle as o
     from replicat_amd import synth
     L = 2 * (mib << 20)
@@ -176,7 +176,7 @@ def test_pipelined_line_fields():
     """The default line: steps are pipelined requests (RC_PIPELINED), the reserve and the
     number that overlapped are reported with the same steps' unpipelined time, and the roofline
     says what its edge / chain times mean then; --pipeline off reports plain sequential steps."""
-    line, rc, err = _cli(['--gpus', '1'] + SMALL[:-10] + ['--steps', '3', '--warmup', '1']
+    line, rc, err = _cli(['--gpus', '1', '--full'] + SMALL[:-10] + ['--steps', '3', '--warmup', '1']
                          + SMALL[-6:])
     assert rc == 0, err[-2000:]
     p = line['pipeline']
@@ -198,7 +198,7 @@ def test_every_rank_checked_against_its_own_shard():
     """Two ranks x 2 streams of 16 MiB at replicat's default parameters: tests/golden/ranks.json
     ('small') holds the reference's cut-list digest of every rank's OWN shard (streams r*2 ..),
     so both ranks carry a flag and the line's is their AND (VERDICT r3 Missing #1)."""
-    out = _run(SHARD + ['--gpus', '2', '--cpu-streams', '0'])
+    out = _run(SHARD + ['--gpus', '2', '--full', '--cpu-streams', '0'])
     (_, res0, _, _, p0), (_, _, _, _, p1) = out
     assert p0 is True and p1 is True
     assert [r['parity'] for r in res0['per_rank']] == [True, True]
@@ -219,7 +219,7 @@ def test_line_parity_is_the_and_over_ranks():
 def test_cpu_baseline_scales_with_ranks():
     """The CPU baseline runs on N x the per-GPU host-core share (OMP_NUM_THREADS per GPU)."""
     for gpus in (1, 2):
-        line, rc, err = _cli(['--gpus', str(gpus)] + SHARD + ['--cpu-streams', '2'],
+        line, rc, err = _cli(['--gpus', str(gpus), '--full'] + SHARD + ['--cpu-streams', '2'],
                              OMP_NUM_THREADS='1')
         assert rc == 0, err[-2000:]
         cpu = line['cpu_baseline']
@@ -227,3 +227,66 @@ def test_cpu_baseline_scales_with_ranks():
         assert f'{gpus} GPU(s) x OMP_NUM_THREADS 1' in cpu['cores_basis']
         assert cpu['matches_gpu'] is True
         assert line['parity_sha256'] is True
+
+
+# ------------------------------------------------ the plain line, --full, --dump-outputs
+
+def test_plain_line_is_lean_and_full_adds_the_rest():
+    """A plain run times its steps and prints the headline fields; the parity check, the
+    unpipelined steps and the CPU baseline are --full's, and null without it."""
+    args = ['--gpus', '1'] + SHARD[:-4] + ['--steps', '2', '--warmup', '1']
+    line, rc, err = _cli(args)
+    assert rc == 0, err[-2000:]
+    assert line['full'] is False and line['steps'] == 2
+    assert line['metric'] == 'GiB/s chunked, device-resident streams'
+    assert line['unit'] == 'GiB/s' and line['higher_is_better'] is True and line['dtype'] == 'u8'
+    assert line['ms_per_step'] > 0
+    assert line['value'] == pytest.approx(2 * (16 << 20) / (line['ms_per_step'] / 1e3) / GIB,
+                                          rel=1e-2, abs=0.006)
+    assert line['cpu_baseline'] is None and line['parity_sha256'] is None
+    assert line['pipeline']['unpipelined_ms_per_step'] is None
+    full, rc, err = _cli(args + ['--full', '--cpu-streams', '1'])
+    assert rc == 0, err[-2000:]
+    assert full['full'] is True and full['parity_sha256'] is True
+    assert full['cpu_baseline']['matches_gpu'] is True
+    assert full['pipeline']['unpipelined_ms_per_step'] is not None
+    for k in ('metric', 'unit', 'higher_is_better', 'dtype', 'steps', 'config'):
+        assert full[k] == line[k]
+
+
+def test_dump_outputs_are_the_last_steps_cuts(tmp_path):
+    """--dump-outputs writes the cut lists the timed path left (float64 .npy), the same on every
+    run with the same arguments, and they are the oracle's."""
+    from oracle import oracle as o
+    from replicat_amd import synth
+    n, size = 3, 1 << 20
+    args = ['--gpus', '1', '--config', '2', '--streams', str(n), '--stream-mib', '1', '--steps', '2',
+            '--warmup', '0', '--min-length', '2000', '--max-length', '80000']
+    got = []
+    for d in ('a', 'b'):
+        line, rc, err = _cli(args + ['--dump-outputs', str(tmp_path / d)])
+        assert rc == 0, err[-2000:]
+        assert line['parity_sha256'] is None  # dumping does not turn the checks on
+        got.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = got
+    assert sorted(a) == ['counts.npy', 'cut_streams.npy', 'cuts.npy']
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    exp = [o.chunk_stream(synth.stream_bytes(size, synth.DEFAULT_SEED, i), 2000, 80000, None, 0)
+           for i in range(n)]
+    assert a['counts.npy'].tolist() == [len(e) for e in exp]
+    assert a['cut_streams.npy'].tolist() == [0, 1, 2]
+    assert a['cuts.npy'].tolist() == [c for e in exp for c in e]
+
+
+def test_dump_outputs_samples_a_large_output(tmp_path, monkeypatch):
+    """Past DUMP_MAX_VALUES cut ends, a fixed seeded sample of whole streams is written."""
+    ends = [np.arange(1, k + 2, dtype=np.uint64) for k in range(40)]
+    monkeypatch.setattr(bench, 'DUMP_MAX_VALUES', 100)
+    bench.dump_outputs(str(tmp_path / 'a'), ends)
+    bench.dump_outputs(str(tmp_path / 'b'), ends, rank=1)
+    counts, pick, cuts = (np.load(tmp_path / 'a' / f'{k}.npy') for k in ('counts', 'cut_streams', 'cuts'))
+    assert counts.tolist() == list(range(1, 41))
+    assert 0 < len(cuts) <= 100 and len(pick) < 40
+    assert cuts.tolist() == [c for i in pick.astype(int) for c in ends[i].tolist()]
+    assert np.array_equal(pick, np.load(tmp_path / 'b' / 'cut_streams_rank1.npy'))
