@@ -1,5 +1,6 @@
 /*
- * replicat_cipher.h -- C ABI of the MI355X (gfx950) AES-GCM chunk encryption.
+ * replicat_cipher.h -- C ABI of the MI355X (gfx950) chunk encryption: AES-GCM, and (second half)
+ * ChaCha20-Poly1305.
  *
  * Replaces, for the snapshot path of encrypted repositories, the per-chunk
  *     encrypted_contents = self.props.encrypt(output_chunk, self.props.derive_shared_subkey(digest))
@@ -83,6 +84,67 @@ int rc_gcm_encrypt_chunks(rc_gcm *g, const rc_chunker *layout, uint64_t n,
  * on the launch stream; read returns the summed milliseconds and clears. */
 int rc_gcm_timing_enable(rc_gcm *g, int enable);
 int rc_gcm_timing_read(rc_gcm *g, double *ms, uint64_t *calls);
+
+/* ---------------------------------------------------------------------------------------------
+ * ChaCha20-Poly1305: replicat's second cipher adapter, `chacha20_poly1305`
+ * (replicat/utils/adapters.py:161-164; registry :321-329; chosen by `encryption.cipher.name`,
+ * repository.py:579-600), again over AEADCipherAdapterMixin:
+ *     encrypt(data, key) = nonce || ChaCha20Poly1305(key).encrypt(nonce, data, None)
+ * RFC 8439 §2.8 with a 256-bit key, a 96-bit nonce and no associated data: the Poly1305 one-time
+ * key is the first 32 bytes of the ChaCha20 block at counter 0, the data is encrypted from
+ * counter 1, and T = Poly1305(pad16(C) || le64(0) || le64(len(C))).  The blob layout
+ * nonce (12) || C || T (16) and every argument list are those of the rc_gcm_* twin; a message may
+ * hold (2^32 - 1) * 64 bytes (the block counter), more is RC_ERR_ARGUMENT.  Implemented by
+ * replicat_amd/csrc/{capi_chacha.cpp,chacha.hip}. */
+
+typedef struct rc_chacha rc_chacha;
+
+int rc_chacha_create(int device, rc_chacha **out);
+void rc_chacha_destroy(rc_chacha *g);
+uint32_t rc_chacha_key_bytes(const rc_chacha *g);   /* 32 */
+uint32_t rc_chacha_nonce_bytes(const rc_chacha *g); /* 12 */
+
+/* As rc_gcm_encrypt_device / rc_gcm_decrypt_device: keys are 32 bytes, nonces 12; d_out[i]
+ * receives 12 + lens[i] + 16 bytes (encrypt) or lens[i] - 28 bytes and d_ok[i] (decrypt; 0 also
+ * for a blob shorter than 28 bytes).  Pointers may have any alignment.  Enqueued on hip_stream. */
+int rc_chacha_encrypt_device(rc_chacha *g, uint64_t n, const uint8_t *const *d_in, const uint64_t *lens,
+                             const uint8_t *const *d_keys, const uint8_t *const *d_nonces,
+                             uint8_t *const *d_out, void *hip_stream);
+int rc_chacha_decrypt_device(rc_chacha *g, uint64_t n, const uint8_t *const *d_in, const uint64_t *lens,
+                             const uint8_t *const *d_keys, uint8_t *const *d_out, uint8_t *d_ok,
+                             void *hip_stream);
+
+/* The same over HOST buffers (blocking).  decrypt fills ok[i] and returns RC_ERR_TAG when any of
+ * them is 0. */
+int rc_chacha_encrypt_host(rc_chacha *g, uint64_t n, const uint8_t *const *in, const uint64_t *lens,
+                           const uint8_t *const *keys, const uint8_t *const *nonces,
+                           uint8_t *const *out);
+int rc_chacha_decrypt_host(rc_chacha *g, uint64_t n, const uint8_t *const *in, const uint64_t *lens,
+                           const uint8_t *const *keys, uint8_t *const *out, uint8_t *ok);
+
+/* As rc_gcm_chunks_layout / rc_gcm_encrypt_chunks with 28 bytes of overhead per chunk: chunk k of
+ * stream i, cut range [s, e), cut slot c = cut_base[i] + k, takes the key at d_keys + 64 c (where
+ * rc_blake2b_derive_chunks leaves it with digest_size 32) and the nonce at d_nonces + 12 c, and
+ * its blob goes to d_out + out_base[i] + s + 28 k.  Counts are read on the device (no host sync):
+ * work is taken as k < count, so a stream whose count is negative (RC_COUNT_OVERFLOW,
+ * RC_COUNT_FAULT) contributes no chunk and nothing of its region is written. */
+uint64_t rc_chacha_chunks_layout(const rc_chacha *g, const rc_chunker *layout, uint64_t n,
+                                 const uint64_t *lens, uint64_t *out_base);
+int rc_chacha_encrypt_chunks(rc_chacha *g, const rc_chunker *layout, uint64_t n,
+                             const uint8_t *const *d_streams, const uint64_t *lens,
+                             const uint64_t *d_cuts, const int64_t *d_counts, const uint8_t *d_keys,
+                             const uint8_t *d_nonces, uint8_t *d_out, void *hip_stream);
+
+int rc_chacha_timing_enable(rc_chacha *g, int enable);
+int rc_chacha_timing_read(rc_chacha *g, double *ms, uint64_t *calls);
+
+/* Test / diagnostic entry (like rc_tables_key and rc_tile_records): the raw one-time-key Poly1305
+ * (RFC 8439 §2.5) of n HOST messages, each under its own 32-byte key r || s (r is clamped here),
+ * tags16[i] receiving 16 bytes; run on the current device by the same device code the AEAD uses.
+ * The AEAD derives r and s from the key, so the corner cases of the reduction mod 2^130 - 5 and
+ * of the final addition cannot be reached through it; they can through this.  Blocking. */
+int rc_poly1305_host(uint64_t n, const uint8_t *const *msgs, const uint64_t *lens,
+                     const uint8_t *const *keys32, uint8_t *const *tags16);
 
 #ifdef __cplusplus
 }

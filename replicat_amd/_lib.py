@@ -100,6 +100,19 @@ SIGNATURES = {
     'rc_gcm_encrypt_chunks': (_int, [_p, _p, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
     'rc_gcm_timing_enable': (_int, [_p, _int]),
     'rc_gcm_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
+    'rc_chacha_create': (_int, [_int, ctypes.POINTER(_p)]),
+    'rc_chacha_destroy': (None, [_p]),
+    'rc_chacha_key_bytes': (_u32, [_p]),
+    'rc_chacha_nonce_bytes': (_u32, [_p]),
+    'rc_chacha_encrypt_device': (_int, [_p, _u64, _p, _p, _p, _p, _p, _p]),
+    'rc_chacha_decrypt_device': (_int, [_p, _u64, _p, _p, _p, _p, _p, _p]),
+    'rc_chacha_encrypt_host': (_int, [_p, _u64, _p, _p, _p, _p, _p]),
+    'rc_chacha_decrypt_host': (_int, [_p, _u64, _p, _p, _p, _p, _p]),
+    'rc_chacha_chunks_layout': (_u64, [_p, _p, _u64, _p, _p]),
+    'rc_chacha_encrypt_chunks': (_int, [_p, _p, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'rc_chacha_timing_enable': (_int, [_p, _int]),
+    'rc_chacha_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
+    'rc_poly1305_host': (_int, [_u64, _p, _p, _p, _p]),
 }
 
 

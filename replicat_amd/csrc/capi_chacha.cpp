@@ -1,110 +1,44 @@
-// capi_cipher.cpp -- host side of include/replicat_cipher.h: AES-GCM on the device.
+// capi_chacha.cpp -- host side of the rc_chacha_* family of include/replicat_cipher.h:
+// ChaCha20-Poly1305 on the device.
 //
-// A handle mirrors replicat's `aes_gcm(key_bits, nonce_bits)` cipher adapter
-// (replicat/utils/adapters.py:117-158): encrypt = nonce || C || T, decrypt with the tag check.
-// Work lists are built here (buffers) or on the device (the chunk lists rc_chunk_device left in
-// HBM); gcm.hip runs them one workgroup per message.  The constant tables the kernel stages into
-// LDS -- the AES T0 table and the GF(2^128) squaring table -- are computed here per handle.
+// A handle mirrors replicat's `chacha20_poly1305` cipher adapter (replicat/utils/adapters.py:161-164
+// over AEADCipherAdapterMixin, :117-148): 256-bit key, 96-bit nonce, encrypt = nonce || C || T,
+// decrypt with the tag check.  Work lists are GcmItem records, built here (buffers) or on the
+// device by the AES-GCM path's list kernel (the chunk lists rc_chunk_device left in HBM: the two
+// ciphers share the blob layout); chacha.hip runs them one wave or one workgroup per message.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <array>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <vector>
 
 #include "../../include/replicat_cipher.h"
 #include "capi_internal.h"
+#include "chacha_kernels.h"
 #include "cipher_host.h"
-#include "knobs.h"
-#include "cipher_kernels.h"
 #include "digest_kernels.h"
+#include "knobs.h"
 
-static_assert(sizeof(GcmItem) == 48, "GcmItem is a 48-byte device record");
+struct rc_chacha : rc_cipher::CipherCore {};
 
 namespace {
 
 using namespace rc_cipher;
 
-// ------------------------------------------------------------------ constant tables
+constexpr uint64_t kKey = 32, kNonce = 12, kOver = kNonce + 16;
 
-uint8_t xt(uint8_t a) { return static_cast<uint8_t>((a << 1) ^ ((a & 0x80) ? 0x1B : 0)); }
-uint8_t gm(uint8_t a, uint8_t b) {
-    uint8_t p = 0;
-    for (; b; b >>= 1, a = xt(a))
-        if (b & 1) p ^= a;
-    return p;
-}
+int check_handle(const rc_chacha *g) { return g ? 0 : rc_fail(RC_ERR_ARGUMENT, "null cipher"); }
 
-// FIPS 197 S-box (§5.1.1: inverse in GF(2^8), then the affine map) and T0[x] = {2s, s, s, 3s}:
-// the first column of MixColumns applied to s = S[x], as a little-endian word
-void make_te0(uint32_t *te0) {
-    uint8_t inv[256] = {0};
-    for (int x = 1; x < 256; ++x)
-        for (int c = 1; c < 256; ++c)
-            if (gm(static_cast<uint8_t>(x), static_cast<uint8_t>(c)) == 1) {
-                inv[x] = static_cast<uint8_t>(c);
-                break;
-            }
-    for (int x = 0; x < 256; ++x) {
-        const uint8_t b = inv[x];
-        uint8_t s = b;
-        for (int i = 1; i <= 4; ++i) s ^= static_cast<uint8_t>((b << i) | (b >> (8 - i)));
-        s ^= 0x63;
-        te0[x] = uint32_t(gm(s, 2)) | (uint32_t(s) << 8) | (uint32_t(s) << 16) | (uint32_t(gm(s, 3)) << 24);
-    }
-}
-
-// SP 800-38D §6.3 product; bit 0 = the MSB of byte 0
-void gf_mul(const uint8_t *X, const uint8_t *Y, uint8_t *Z) {
-    uint8_t V[16], acc[16] = {0};
-    std::memcpy(V, Y, 16);
-    for (int i = 0; i < 128; ++i) {
-        if (X[i / 8] & (0x80 >> (i % 8)))
-            for (int j = 0; j < 16; ++j) acc[j] ^= V[j];
-        const int lsb = V[15] & 1;
-        for (int j = 15; j > 0; --j) V[j] = static_cast<uint8_t>((V[j] >> 1) | (V[j - 1] << 7));
-        V[0] >>= 1;
-        if (lsb) V[0] ^= 0xE1;
-    }
-    std::memcpy(Z, acc, 16);
-}
-
-// Squaring is GF(2)-linear: entry (j, v) = E(j, v)^2 for the element whose nibble j (the high
-// nibble of byte j / 2 for even j, the low one for odd j) is v; bytes in memory order.
-void make_sq(uint32_t *sq) {
-    for (int j = 0; j < 32; ++j)
-        for (int v = 0; v < 16; ++v) {
-            uint8_t e[16] = {0}, z[16];
-            e[j / 2] = static_cast<uint8_t>(j & 1 ? v : v << 4);
-            gf_mul(e, e, z);
-            std::memcpy(sq + 4 * (16 * j + v), z, 16);
-        }
-}
-
-constexpr size_t kTe0Words = 256, kSqWords = 2048;
-
-}  // namespace
-
-struct rc_gcm : rc_cipher::CipherCore {
-    uint32_t key_bytes = 32, nonce_bytes = 12;
-    rc_cipher::DevBuf d_consts;  // te0 | sq
-};
-
-namespace {
-
-GcmArgs base_args(const rc_gcm *g) {
-    GcmArgs a{};
-    a.te0 = static_cast<const uint32_t *>(g->d_consts.p);
-    a.sq = a.te0 + kTe0Words;
-    a.nonce_bytes = g->nonce_bytes;
-    return a;
+int check_len(uint64_t i, uint64_t len) {
+    if (len <= kChaMaxLen) return 0;
+    return rc_fail(RC_ERR_ARGUMENT, "item %llu: %llu bytes exceed the 32-bit block counter",
+                   (unsigned long long)i, (unsigned long long)len);
 }
 
 // n host-built items, longest first (the kernel hands them out in list order)
-int enqueue_items(rc_gcm *g, bool dec, std::vector<GcmItem> &items, uint8_t *d_ok, hipStream_t st) {
+int enqueue_items(rc_chacha *g, int mode, std::vector<GcmItem> &items, uint8_t *d_ok, hipStream_t st) {
     const uint64_t n = items.size();
     if (!n) return 0;
     std::stable_sort(items.begin(), items.end(),
@@ -118,35 +52,25 @@ int enqueue_items(rc_gcm *g, bool dec, std::vector<GcmItem> &items, uint8_t *d_o
     std::memset(h, 0, 16);  // header (reserved)
     std::memcpy(h + 16, items.data(), n * sizeof(GcmItem));
     RC_HIP_TRY(hipMemcpyAsync(w->d_stage.p, h, bytes, hipMemcpyHostToDevice, st));
-    uint8_t *d = static_cast<uint8_t *>(w->d_stage.p);
-    GcmArgs a = base_args(g);
-    a.items = reinterpret_cast<const GcmItem *>(d + 16);
+    ChaArgs a{};
+    a.items = reinterpret_cast<const GcmItem *>(static_cast<uint8_t *>(w->d_stage.p) + 16);
+    a.n = n;
     a.ok = d_ok;
     std::array<hipEvent_t, 2> ev{};
     if (int rc = timing_begin(g, st, ev)) return rc;
-    if (n > 0x7FFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "%llu messages in one call", (unsigned long long)n);
-    const unsigned groups = static_cast<unsigned>(n);
-    GCM_DBG("launch %s n=%llu groups=%u", dec ? "decrypt" : "encrypt", (unsigned long long)n, groups);
-    if (rc_gcm_launch(g->key_bytes, dec, a, groups, st))
-        return rc_fail(RC_ERR_HIP, "%s", rc_gcm_launch_error());
+    GCM_DBG("chacha launch mode=%d n=%llu", mode, (unsigned long long)n);
+    if (rc_chacha_launch(mode, a, st)) return rc_fail(RC_ERR_HIP, "%s", rc_chacha_launch_error());
     if (int rc = timing_end(g, st, ev)) return rc;
     return finish(*w, st);
 }
-
-int check_handle(const rc_gcm *g) { return g ? 0 : rc_fail(RC_ERR_ARGUMENT, "null cipher"); }
 
 }  // namespace
 
 extern "C" {
 
-int rc_gcm_create(uint32_t key_bits, uint32_t nonce_bits, int device, rc_gcm **out) {
+int rc_chacha_create(int device, rc_chacha **out) {
     if (!out) return rc_fail(RC_ERR_ARGUMENT, "null output handle");
     *out = nullptr;
-    if (key_bits != 128 && key_bits != 192 && key_bits != 256)
-        return rc_fail(RC_ERR_KEY_SIZE, "Invalid key size");
-    const uint32_t nonce_bytes = nonce_bits / 8;
-    if (nonce_bytes < 8 || nonce_bytes > 128)
-        return rc_fail(RC_ERR_NONCE_SIZE, "Nonce must be between 8 and 128 bytes");
     {  // the environment knobs (knobs.h): a malformed one fails every handle's creation
         rc::Knobs knobs;
         char err[256];
@@ -156,50 +80,36 @@ int rc_gcm_create(uint32_t key_bits, uint32_t nonce_bits, int device, rc_gcm **o
     if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
         return rc_fail(RC_ERR_NO_DEVICE, "no HIP device %d", device);
     DeviceGuard guard(device);
-    rc_gcm *g = new rc_gcm;
-    g->key_bytes = key_bits / 8;
-    g->nonce_bytes = nonce_bytes;
+    rc_chacha *g = new rc_chacha;
     g->device = device;
-    std::vector<uint32_t> consts(kTe0Words + kSqWords);
-    make_te0(consts.data());
-    make_sq(consts.data() + kTe0Words);
-    int rc = g->d_consts.ensure(consts.size() * sizeof(uint32_t));
-    if (!rc) {
-        const hipError_t e = hipMemcpy(g->d_consts.p, consts.data(), consts.size() * sizeof(uint32_t),
-                                       hipMemcpyHostToDevice);
-        if (e != hipSuccess) rc = rc_fail(RC_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
-    }
-    if (!rc) rc = core_create_events(g);
-    if (rc) {
-        rc_gcm_destroy(g);
+    if (int rc = core_create_events(g)) {
+        rc_chacha_destroy(g);
         return rc;
     }
-    rc_track(g, [](void *p) { rc_gcm_destroy(static_cast<rc_gcm *>(p)); });
+    rc_track(g, [](void *p) { rc_chacha_destroy(static_cast<rc_chacha *>(p)); });
     *out = g;
     return RC_OK;
 }
 
-void rc_gcm_destroy(rc_gcm *g) {
+void rc_chacha_destroy(rc_chacha *g) {
     if (!g) return;
     rc_untrack(g);
     {
-        // a call still running on another thread (a daemon thread when the exit hook runs)
-        // finishes first: its buffers and streams go only after it
+        // a call still running on another thread finishes first (as rc_gcm_destroy)
         std::lock_guard<std::mutex> lock(g->mu);
         DeviceGuard guard(g->device);
         (void)hipDeviceSynchronize();
-        g->d_consts.release();
         core_release(g);
     }
     delete g;
 }
 
-uint32_t rc_gcm_key_bytes(const rc_gcm *g) { return g ? g->key_bytes : 0; }
-uint32_t rc_gcm_nonce_bytes(const rc_gcm *g) { return g ? g->nonce_bytes : 0; }
+uint32_t rc_chacha_key_bytes(const rc_chacha *g) { return g ? uint32_t(kKey) : 0; }
+uint32_t rc_chacha_nonce_bytes(const rc_chacha *g) { return g ? uint32_t(kNonce) : 0; }
 
-int rc_gcm_encrypt_device(rc_gcm *g, uint64_t n, const uint8_t *const *d_in, const uint64_t *lens,
-                          const uint8_t *const *d_keys, const uint8_t *const *d_nonces,
-                          uint8_t *const *d_out, void *hip_stream) {
+int rc_chacha_encrypt_device(rc_chacha *g, uint64_t n, const uint8_t *const *d_in, const uint64_t *lens,
+                             const uint8_t *const *d_keys, const uint8_t *const *d_nonces,
+                             uint8_t *const *d_out, void *hip_stream) {
     if (int rc = check_handle(g)) return rc;
     if (n == 0) return RC_OK;
     if (!d_in || !lens || !d_keys || !d_nonces || !d_out) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
@@ -207,57 +117,59 @@ int rc_gcm_encrypt_device(rc_gcm *g, uint64_t n, const uint8_t *const *d_in, con
     for (uint64_t i = 0; i < n; ++i) {
         if ((lens[i] && !d_in[i]) || !d_keys[i] || !d_nonces[i] || !d_out[i])
             return rc_fail(RC_ERR_ARGUMENT, "item %llu: null pointer", (unsigned long long)i);
+        if (int rc = check_len(i, lens[i])) return rc;
         items[i] = GcmItem{addr(d_in[i]), lens[i], addr(d_out[i]), addr(d_keys[i]), addr(d_nonces[i]), i};
     }
     std::lock_guard<std::mutex> lock(g->mu);
     DeviceGuard guard(g->device);
-    return enqueue_items(g, false, items, nullptr, static_cast<hipStream_t>(hip_stream));
+    return enqueue_items(g, kChaEncrypt, items, nullptr, static_cast<hipStream_t>(hip_stream));
 }
 
-int rc_gcm_decrypt_device(rc_gcm *g, uint64_t n, const uint8_t *const *d_in, const uint64_t *lens,
-                          const uint8_t *const *d_keys, uint8_t *const *d_out, uint8_t *d_ok,
-                          void *hip_stream) {
+int rc_chacha_decrypt_device(rc_chacha *g, uint64_t n, const uint8_t *const *d_in, const uint64_t *lens,
+                             const uint8_t *const *d_keys, uint8_t *const *d_out, uint8_t *d_ok,
+                             void *hip_stream) {
     if (int rc = check_handle(g)) return rc;
     if (n == 0) return RC_OK;
     if (!d_in || !lens || !d_keys || !d_out || !d_ok) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
-    const uint64_t over = g->nonce_bytes + 16;
     std::vector<GcmItem> items;
     items.reserve(n);
     for (uint64_t i = 0; i < n; ++i) {
-        if (lens[i] < over) continue;  // too short to hold nonce and tag: ok stays 0 (InvalidTag)
-        const uint64_t len = lens[i] - over;
+        if (lens[i] < kOver) continue;  // too short to hold nonce and tag: ok stays 0 (InvalidTag)
+        const uint64_t len = lens[i] - kOver;
         if (!d_in[i] || !d_keys[i] || (len && !d_out[i]))
             return rc_fail(RC_ERR_ARGUMENT, "item %llu: null pointer", (unsigned long long)i);
+        if (int rc = check_len(i, len)) return rc;
         items.push_back(GcmItem{addr(d_in[i]), len, addr(d_out[i]), addr(d_keys[i]), 0, i});
     }
     std::lock_guard<std::mutex> lock(g->mu);
     DeviceGuard guard(g->device);
     const hipStream_t st = static_cast<hipStream_t>(hip_stream);
     RC_HIP_TRY(hipMemsetAsync(d_ok, 0, n, st));
-    return enqueue_items(g, true, items, d_ok, st);
+    return enqueue_items(g, kChaDecrypt, items, d_ok, st);
 }
 
-int rc_gcm_encrypt_host(rc_gcm *g, uint64_t n, const uint8_t *const *in, const uint64_t *lens,
-                        const uint8_t *const *keys, const uint8_t *const *nonces, uint8_t *const *out) {
+int rc_chacha_encrypt_host(rc_chacha *g, uint64_t n, const uint8_t *const *in, const uint64_t *lens,
+                           const uint8_t *const *keys, const uint8_t *const *nonces, uint8_t *const *out) {
     if (int rc = check_handle(g)) return rc;
     if (n == 0) return RC_OK;
     if (!in || !lens || !keys || !nonces || !out) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
-    for (uint64_t i = 0; i < n; ++i)
+    for (uint64_t i = 0; i < n; ++i) {
         if ((lens[i] && !in[i]) || !keys[i] || !nonces[i] || !out[i])
             return rc_fail(RC_ERR_ARGUMENT, "item %llu: null pointer", (unsigned long long)i);
+        if (int rc = check_len(i, lens[i])) return rc;
+    }
     std::lock_guard<std::mutex> lock(g->mu);
     DeviceGuard guard(g->device);
-    const uint64_t kb = g->key_bytes, nb = g->nonce_bytes;
-    // input image: messages (16-aligned) | keys (64 B each) | nonces (128 B each)
+    // input image: messages (16-aligned) | keys (32 B each) | nonces (16 B each)
     std::vector<uint64_t> in_off(n), out_off(n);
     uint64_t a = 0, b = 0;
     for (uint64_t i = 0; i < n; ++i) {
         in_off[i] = a;
         a += up16(lens[i]);
         out_off[i] = b;
-        b += up16(nb + lens[i] + 16);
+        b += up16(kOver + lens[i]);
     }
-    const uint64_t key_off = a, nonce_off = a + 64 * n, in_total = nonce_off + 128 * n;
+    const uint64_t key_off = a, nonce_off = a + kKey * n, in_total = nonce_off + 16 * n;
     if (int rc = g->h_in.ensure(in_total)) return rc;
     if (int rc = g->d_in.ensure(in_total)) return rc;
     if (int rc = g->h_out.ensure(b)) return rc;
@@ -265,45 +177,42 @@ int rc_gcm_encrypt_host(rc_gcm *g, uint64_t n, const uint8_t *const *in, const u
     uint8_t *hi = static_cast<uint8_t *>(g->h_in.p), *ho = static_cast<uint8_t *>(g->h_out.p);
     for (uint64_t i = 0; i < n; ++i) {
         if (lens[i]) std::memcpy(hi + in_off[i], in[i], lens[i]);
-        std::memcpy(hi + key_off + 64 * i, keys[i], kb);
-        std::memcpy(hi + nonce_off + 128 * i, nonces[i], nb);
+        std::memcpy(hi + key_off + kKey * i, keys[i], kKey);
+        std::memcpy(hi + nonce_off + 16 * i, nonces[i], kNonce);
     }
-    GCM_DBG("encrypt_host: upload %llu bytes", (unsigned long long)in_total);
     RC_HIP_TRY(hipMemcpyAsync(g->d_in.p, hi, in_total, hipMemcpyHostToDevice, nullptr));
     const uint64_t D = addr(g->d_in.p), O = addr(g->d_out.p);
     std::vector<GcmItem> items(n);
     for (uint64_t i = 0; i < n; ++i)
-        items[i] = GcmItem{D + in_off[i], lens[i], O + out_off[i], D + key_off + 64 * i,
-                           D + nonce_off + 128 * i, i};
-    if (int rc = enqueue_items(g, false, items, nullptr, nullptr)) return rc;
-    GCM_DBG("encrypt_host: download %llu bytes", (unsigned long long)b);
+        items[i] = GcmItem{D + in_off[i], lens[i], O + out_off[i], D + key_off + kKey * i,
+                           D + nonce_off + 16 * i, i};
+    if (int rc = enqueue_items(g, kChaEncrypt, items, nullptr, nullptr)) return rc;
     RC_HIP_TRY(hipMemcpyAsync(ho, g->d_out.p, b, hipMemcpyDeviceToHost, nullptr));
-    GCM_DBG("encrypt_host: synchronize");
     RC_HIP_TRY(hipStreamSynchronize(nullptr));
-    GCM_DBG("encrypt_host: done");
-    for (uint64_t i = 0; i < n; ++i) std::memcpy(out[i], ho + out_off[i], nb + lens[i] + 16);
+    for (uint64_t i = 0; i < n; ++i) std::memcpy(out[i], ho + out_off[i], kOver + lens[i]);
     return RC_OK;
 }
 
-int rc_gcm_decrypt_host(rc_gcm *g, uint64_t n, const uint8_t *const *in, const uint64_t *lens,
-                        const uint8_t *const *keys, uint8_t *const *out, uint8_t *ok) {
+int rc_chacha_decrypt_host(rc_chacha *g, uint64_t n, const uint8_t *const *in, const uint64_t *lens,
+                           const uint8_t *const *keys, uint8_t *const *out, uint8_t *ok) {
     if (int rc = check_handle(g)) return rc;
     if (n == 0) return RC_OK;
     if (!in || !lens || !keys || !out || !ok) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
     std::lock_guard<std::mutex> lock(g->mu);
     DeviceGuard guard(g->device);
-    const uint64_t kb = g->key_bytes, over = g->nonce_bytes + 16;
     std::vector<uint64_t> in_off(n), out_off(n);
     uint64_t a = 0, b = 0;
     for (uint64_t i = 0; i < n; ++i) {
-        if ((lens[i] && !in[i]) || !keys[i] || (lens[i] > over && !out[i]))
+        if ((lens[i] && !in[i]) || !keys[i] || (lens[i] > kOver && !out[i]))
             return rc_fail(RC_ERR_ARGUMENT, "item %llu: null pointer", (unsigned long long)i);
+        if (lens[i] >= kOver)
+            if (int rc = check_len(i, lens[i] - kOver)) return rc;
         in_off[i] = a;
         a += up16(lens[i]);
         out_off[i] = b;
-        b += up16(lens[i] >= over ? lens[i] - over : 0);
+        b += up16(lens[i] >= kOver ? lens[i] - kOver : 0);
     }
-    const uint64_t key_off = a, in_total = a + 64 * n;
+    const uint64_t key_off = a, in_total = a + kKey * n;
     if (int rc = g->h_in.ensure(in_total)) return rc;
     if (int rc = g->d_in.ensure(in_total)) return rc;
     if (int rc = g->h_out.ensure(b + 16)) return rc;
@@ -312,7 +221,7 @@ int rc_gcm_decrypt_host(rc_gcm *g, uint64_t n, const uint8_t *const *in, const u
     uint8_t *hi = static_cast<uint8_t *>(g->h_in.p), *ho = static_cast<uint8_t *>(g->h_out.p);
     for (uint64_t i = 0; i < n; ++i) {
         if (lens[i]) std::memcpy(hi + in_off[i], in[i], lens[i]);
-        std::memcpy(hi + key_off + 64 * i, keys[i], kb);
+        std::memcpy(hi + key_off + kKey * i, keys[i], kKey);
     }
     const hipStream_t st = nullptr;
     RC_HIP_TRY(hipMemcpyAsync(g->d_in.p, hi, in_total, hipMemcpyHostToDevice, st));
@@ -322,48 +231,49 @@ int rc_gcm_decrypt_host(rc_gcm *g, uint64_t n, const uint8_t *const *in, const u
     std::vector<GcmItem> items;
     items.reserve(n);
     for (uint64_t i = 0; i < n; ++i)
-        if (lens[i] >= over)
-            items.push_back(GcmItem{D + in_off[i], lens[i] - over, O + out_off[i], D + key_off + 64 * i, 0, i});
-    if (int rc = enqueue_items(g, true, items, d_ok, st)) return rc;
+        if (lens[i] >= kOver)
+            items.push_back(GcmItem{D + in_off[i], lens[i] - kOver, O + out_off[i], D + key_off + kKey * i, 0, i});
+    if (int rc = enqueue_items(g, kChaDecrypt, items, d_ok, st)) return rc;
     if (b) RC_HIP_TRY(hipMemcpyAsync(ho, g->d_out.p, b, hipMemcpyDeviceToHost, st));
     RC_HIP_TRY(hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st));
     RC_HIP_TRY(hipStreamSynchronize(st));
     bool all = true;
     for (uint64_t i = 0; i < n; ++i) {
-        if (lens[i] > over) std::memcpy(out[i], ho + out_off[i], lens[i] - over);
+        if (lens[i] > kOver) std::memcpy(out[i], ho + out_off[i], lens[i] - kOver);
         all = all && ok[i];
     }
     return all ? RC_OK : rc_fail(RC_ERR_TAG, "tag mismatch (InvalidTag)");
 }
 
-uint64_t rc_gcm_chunks_layout(const rc_gcm *g, const rc_chunker *layout, uint64_t n,
-                              const uint64_t *lens, uint64_t *out_base) {
+uint64_t rc_chacha_chunks_layout(const rc_chacha *g, const rc_chunker *layout, uint64_t n,
+                                 const uint64_t *lens, uint64_t *out_base) {
     if (!g || !layout || !lens || !n) return 0;
     std::vector<uint64_t> caps(n);
     rc_cut_capacity(layout, n, lens, caps.data());
-    const uint64_t over = g->nonce_bytes + 16;
     uint64_t acc = 0;
     for (uint64_t i = 0; i < n; ++i) {
         if (out_base) out_base[i] = acc;
-        acc = up16(acc + lens[i] + caps[i] * over);  // 16-aligned regions keep the fast path
+        acc = up16(acc + lens[i] + caps[i] * kOver);  // 16-aligned regions keep the fast path
     }
     return acc;
 }
 
-int rc_gcm_encrypt_chunks(rc_gcm *g, const rc_chunker *layout, uint64_t n,
-                          const uint8_t *const *d_streams, const uint64_t *lens,
-                          const uint64_t *d_cuts, const int64_t *d_counts, const uint8_t *d_keys,
-                          const uint8_t *d_nonces, uint8_t *d_out, void *hip_stream) {
+int rc_chacha_encrypt_chunks(rc_chacha *g, const rc_chunker *layout, uint64_t n,
+                             const uint8_t *const *d_streams, const uint64_t *lens,
+                             const uint64_t *d_cuts, const int64_t *d_counts, const uint8_t *d_keys,
+                             const uint8_t *d_nonces, uint8_t *d_out, void *hip_stream) {
     if (!g || !layout) return rc_fail(RC_ERR_ARGUMENT, "null cipher or chunker");
     if (n == 0) return RC_OK;
     if (!d_streams || !lens || !d_cuts || !d_counts || !d_keys || !d_nonces || !d_out)
         return rc_fail(RC_ERR_ARGUMENT, "null arrays");
-    for (uint64_t i = 0; i < n; ++i)
+    for (uint64_t i = 0; i < n; ++i) {
         if (lens[i] && !d_streams[i])
             return rc_fail(RC_ERR_ARGUMENT, "stream %llu: null pointer", (unsigned long long)i);
+        if (int rc = check_len(i, lens[i])) return rc;  // a chunk is no longer than its stream
+    }
     std::vector<uint64_t> caps(n), out_base(n);
     const uint64_t total_cap = rc_cut_capacity(layout, n, lens, caps.data());
-    rc_gcm_chunks_layout(g, layout, n, lens, out_base.data());
+    rc_chacha_chunks_layout(g, layout, n, lens, out_base.data());
     std::lock_guard<std::mutex> lock(g->mu);
     DeviceGuard guard(g->device);
     const hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -391,6 +301,8 @@ int rc_gcm_encrypt_chunks(rc_gcm *g, const rc_chunker *layout, uint64_t n,
     GcmItem *items = reinterpret_cast<GcmItem *>(d + items_off);
     std::array<hipEvent_t, 2> ev{};
     if (int rc = timing_begin(g, st, ev)) return rc;
+    // chunk_off = the exclusive scan of max(count, 0): a stream whose count is negative
+    // (RC_COUNT_OVERFLOW, RC_COUNT_FAULT) contributes no item, and the kernel takes k < total
     if (rc_b2_launch_scan(d_counts, n, chunk_off, st)) return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
     GcmChunkLists c{};
     c.ptrs = du;
@@ -404,29 +316,78 @@ int rc_gcm_encrypt_chunks(rc_gcm *g, const rc_chunker *layout, uint64_t n,
     c.keys = addr(d_keys);
     c.nonces = addr(d_nonces);
     c.out = addr(d_out);
-    c.nonce_bytes = g->nonce_bytes;
+    c.nonce_bytes = uint32_t(kNonce);
     if (rc_gcm_launch_chunk_items(c, items, st)) return rc_fail(RC_ERR_HIP, "%s", rc_gcm_launch_error());
-    GcmArgs a = base_args(g);
+    ChaArgs a{};
     a.items = items;
     a.d_total = chunk_off + n;
-    if (total_cap > 0x7FFFFFFFull)
-        return rc_fail(RC_ERR_ARGUMENT, "%llu chunk slots in one call", (unsigned long long)total_cap);
-    const unsigned groups = static_cast<unsigned>(std::max<uint64_t>(total_cap, 1));
-    if (rc_gcm_launch(g->key_bytes, false, a, groups, st))
-        return rc_fail(RC_ERR_HIP, "%s", rc_gcm_launch_error());
+    a.n = total_cap;
+    if (rc_chacha_launch(kChaEncrypt, a, st)) return rc_fail(RC_ERR_HIP, "%s", rc_chacha_launch_error());
     if (int rc = timing_end(g, st, ev)) return rc;
     return finish(*w, st);
 }
 
-int rc_gcm_timing_enable(rc_gcm *g, int enable) {
+int rc_chacha_timing_enable(rc_chacha *g, int enable) {
     if (int rc = check_handle(g)) return rc;
     g->timing = enable != 0;
     return RC_OK;
 }
 
-int rc_gcm_timing_read(rc_gcm *g, double *ms, uint64_t *calls) {
+int rc_chacha_timing_read(rc_chacha *g, double *ms, uint64_t *calls) {
     if (int rc = check_handle(g)) return rc;
     return core_timing_read(g, ms, calls);
+}
+
+int rc_poly1305_host(uint64_t n, const uint8_t *const *msgs, const uint64_t *lens,
+                     const uint8_t *const *keys32, uint8_t *const *tags16) {
+    if (n == 0) return RC_OK;
+    if (!msgs || !lens || !keys32 || !tags16) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    for (uint64_t i = 0; i < n; ++i) {
+        if ((lens[i] && !msgs[i]) || !keys32[i] || !tags16[i])
+            return rc_fail(RC_ERR_ARGUMENT, "item %llu: null pointer", (unsigned long long)i);
+        if (int rc = check_len(i, lens[i])) return rc;
+    }
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return rc_fail(RC_ERR_NO_DEVICE, "no HIP device");
+    rc_chacha *g = nullptr;
+    if (int rc = rc_chacha_create(device, &g)) return rc;
+    int rc = RC_OK;
+    {
+        std::lock_guard<std::mutex> lock(g->mu);
+        DeviceGuard guard(g->device);
+        // image: messages (16-aligned) | keys (32 B each); tags 16 B each
+        std::vector<uint64_t> in_off(n);
+        uint64_t a = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            in_off[i] = a;
+            a += up16(lens[i]);
+        }
+        const uint64_t key_off = a, in_total = a + kKey * n;
+        auto run = [&]() -> int {
+            if (int e = g->h_in.ensure(in_total)) return e;
+            if (int e = g->d_in.ensure(in_total)) return e;
+            if (int e = g->h_out.ensure(16 * n)) return e;
+            if (int e = g->d_out.ensure(16 * n)) return e;
+            uint8_t *hi = static_cast<uint8_t *>(g->h_in.p), *ho = static_cast<uint8_t *>(g->h_out.p);
+            for (uint64_t i = 0; i < n; ++i) {
+                if (lens[i]) std::memcpy(hi + in_off[i], msgs[i], lens[i]);
+                std::memcpy(hi + key_off + kKey * i, keys32[i], kKey);
+            }
+            RC_HIP_TRY(hipMemcpyAsync(g->d_in.p, hi, in_total, hipMemcpyHostToDevice, nullptr));
+            const uint64_t D = addr(g->d_in.p), O = addr(g->d_out.p);
+            std::vector<GcmItem> items(n);
+            for (uint64_t i = 0; i < n; ++i)
+                items[i] = GcmItem{D + in_off[i], lens[i], O + 16 * i, D + key_off + kKey * i, 0, i};
+            if (int e = enqueue_items(g, kChaPoly, items, nullptr, nullptr)) return e;
+            RC_HIP_TRY(hipMemcpyAsync(ho, g->d_out.p, 16 * n, hipMemcpyDeviceToHost, nullptr));
+            RC_HIP_TRY(hipStreamSynchronize(nullptr));
+            for (uint64_t i = 0; i < n; ++i) std::memcpy(tags16[i], ho + 16 * i, 16);
+            return RC_OK;
+        };
+        rc = run();
+    }
+    rc_chacha_destroy(g);
+    return rc;
 }
 
 }  // extern "C"

@@ -156,16 +156,35 @@ class ChunkRecord:
             pass
 
 
+CIPHERS = ('aes_gcm', 'chacha20_poly1305')
+
+
 @dataclass
 class ChunkEncryption:
     """What an encrypted repository's snapshot loop needs to encrypt chunks
     (repository.py:1470-1473): KeyProps.params['shared_key'] and ['shared_kdf_params']
     (repository.py:132-137) and the cipher's aes_gcm settings (adapters.py:151-158).  The shared
-    KDF is blake2b(length=key_bits // 8) (repository.py:623-627)."""
+    KDF is blake2b(length=key_bits // 8) (repository.py:623-627).  ``cipher`` is the repository's
+    `encryption.cipher.name` (repository.py:579-600): 'aes_gcm' or 'chacha20_poly1305'
+    (adapters.py:161-164), which has one key size and one nonce size."""
     shared_key: bytes
     shared_kdf_params: bytes
     key_bits: int = 256
     nonce_bits: int = 96
+    cipher: str = 'aes_gcm'
+
+    def __post_init__(self):
+        if self.cipher not in CIPHERS:
+            raise ValueError(f'unknown cipher {self.cipher!r}: one of {", ".join(CIPHERS)}')
+        if self.cipher == 'chacha20_poly1305' and (self.key_bits != 256 or self.nonce_bits != 96):
+            raise ValueError('chacha20_poly1305 takes a 256-bit key and a 96-bit nonce')
+
+    def make_cipher(self, device):
+        """The device cipher these settings name."""
+        from . import cipher as c
+        if self.cipher == 'chacha20_poly1305':
+            return c.GpuChaCha20Poly1305(device=device)
+        return c.GpuAesGcm(key_bits=self.key_bits, nonce_bits=self.nonce_bits, device=device)
 
 
 @dataclass
@@ -320,10 +339,8 @@ class _Slot:
             self.d_nonces = torch.empty(total * nb, dtype=torch.uint8, device=dev)
             self.d_enc = torch.empty(max(prod.enc_cap, 1), dtype=torch.uint8, device=dev)
             self.h_enc = torch.empty(max(prod.enc_cap, 1), dtype=torch.uint8, pin_memory=True)
-            from .cipher import GpuAesGcm
             self.kdf_hasher = GpuBlake2b(length=prod.digest_size, device=prod.device)
-            self.cipher = GpuAesGcm(key_bits=prod.encryption.key_bits,
-                                    nonce_bits=prod.encryption.nonce_bits, device=prod.device)
+            self.cipher = prod.encryption.make_cipher(prod.device)
         self.lease = _Lease()  # stream(): records still viewing host / h_enc
         self.reset(prod.head)
 
@@ -396,11 +413,9 @@ class DeviceSnapshotProducer:
         self._init_state = np.frombuffer(state_init(digest_size), dtype=np.uint8)
         self.encryption = encryption
         if encryption is not None:
-            from .cipher import GpuAesGcm
             # the layout of the ciphertexts (nonce || C || T per chunk); each slot encrypts with
             # its own handle
-            self.cipher = GpuAesGcm(key_bits=encryption.key_bits, nonce_bits=encryption.nonce_bits,
-                                    device=self.device)
+            self.cipher = encryption.make_cipher(self.device)
             kdf = state_init(self.cipher.key_bytes, key=encryption.shared_key,
                              salt=encryption.shared_kdf_params)
             self.d_kdf = torch.from_numpy(np.frombuffer(kdf, dtype=np.uint8).copy()).to(self.dev)
