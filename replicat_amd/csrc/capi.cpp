@@ -1106,9 +1106,20 @@ int chunk_host_impl(rc_chunker *ch, rc_hasher *hasher, uint64_t n, const uint8_t
     DeviceGuard g(ch->device);
     for (int i = 0; i < 2; ++i)
         if (!ch->hstream[i]) HIP_TRY(hipStreamCreateWithFlags(&ch->hstream[i], hipStreamNonBlocking));
+    // an error return leaves no copy into the caller's arrays pending: whatever either slot
+    // has enqueued is waited for first (the error already recorded is the one reported)
+    struct Drain {
+        rc_chunker *ch;
+        bool armed = true;
+        ~Drain() {
+            if (!armed) return;
+            for (hipStream_t s : ch->hstream)
+                if (s) (void)hipStreamSynchronize(s);
+        }
+    } drain{ch};
 
     // batches of whole streams, each up to `budget` bytes (one stream may exceed it alone)
-    const uint64_t budget = 1ull << 30;
+    const uint64_t budget = uint64_t(ch->knobs[knHostBatchBytes]);
     std::vector<uint64_t> cut_base(n + 1, 0);
     for (uint64_t i = 0; i < n; ++i) cut_base[i + 1] = cut_base[i] + cut_cap_of(ch->min_length, lens[i]);
 
@@ -1190,6 +1201,7 @@ int chunk_host_impl(rc_chunker *ch, rc_hasher *hasher, uint64_t n, const uint8_t
     }
     if (int rc = finish(0)) return rc;
     if (int rc = finish(1)) return rc;
+    drain.armed = false;  // both slots waited for
     return RC_OK;
 }
 

@@ -38,6 +38,7 @@ enum Knob : int {
     knTileStreams,    // RC_TILE_STREAMS
     knTileGroup,      // RC_TILE_GROUP
     knTileMask,       // RC_TILE_MASK
+    knHostBatchBytes, // RC_HOST_BATCH_BYTES
     kKnobCount
 };
 
@@ -102,6 +103,10 @@ inline constexpr KnobSpec kKnobTable[kKnobCount] = {
      "(its own queue with every CU in its mask) or plain (a non-blocking stream on the shared "
      "queues); with full / plain the tile kernel's workgroups take every CU the chain kernels "
      "leave (measurement switch)"},
+    {"RC_HOST_BATCH_BYTES", int64_t(1) << 30, 16, int64_t(1) << 40, nullptr,
+     "rc_chunk_host / rc_chunk_digest_host: bytes of whole streams per double-buffered batch "
+     "(a stream longer than this is a batch of its own); test switch: a small value sends a "
+     "few MiB through many batches, so the suite can check slot reuse and output offsets"},
 };
 // clang-format on
 

@@ -3,7 +3,9 @@
 Known answers: FIPS 197 Appendix C (AES-128/192/256 of one block) and the SP 800-38D test
 vectors of McGrew & Viega (test cases 1, 2, 13, 14).  Fixtures: tests/golden/gcm.json, made by
 tests/golden/make_gcm_golden.py with the host's OpenSSL libcrypto -- the library `cryptography`'s
-AESGCM binds, which replicat's aes_gcm adapter calls (replicat/utils/adapters.py:127-144)."""
+AESGCM binds, which replicat's aes_gcm adapter calls (replicat/utils/adapters.py:127-144).
+tests/golden/gcm_corners.json (same generator): nonces solved so that inc32 wraps inside the
+message, and nonce lengths around the 16-byte blocks of J0's GHASH."""
 import hashlib
 import random
 
@@ -30,6 +32,7 @@ GCM_KAT = [  # key, iv, plaintext, C || T (McGrew & Viega test cases 1, 2, 13, 1
 ]
 
 GCM = G.load('gcm.json')
+CORNERS = G.load('gcm_corners.json')
 
 
 def plaintext(case):
@@ -50,8 +53,8 @@ def test_sp800_38d_vectors(oracle, key, iv, pt, out):
     assert oracle.gcm_decrypt(k, v, bytes.fromhex(out)) == p
 
 
-@pytest.mark.parametrize('case', [c for c in GCM['cases'] if c.get('pt_len', 0) <= 200_000],
-                         ids=lambda c: c['name'])
+@pytest.mark.parametrize('case', [c for c in GCM['cases'] if c.get('pt_len', 0) <= 200_000]
+                         + CORNERS['cases'], ids=lambda c: c['name'])
 def test_openssl_fixtures(oracle, case):
     key, iv, pt = bytes.fromhex(case['key']), bytes.fromhex(case['iv']), plaintext(case)
     out = oracle.gcm_encrypt(key, iv, pt)
@@ -69,6 +72,31 @@ def test_fixture_set_covers_the_edges():
         for ivn in (8, 12, 13, 16, 60, 128):
             assert f'k{kb}_iv{ivn}_p0' in names and f'k{kb}_iv{ivn}_p16385' in names
     assert any(c.get('pt_len') == 5_120_000 for c in GCM['cases'])
+
+
+def test_corner_set_covers_the_wraps():
+    """The counter word of J0 (recorded by the generator, which checked it against OpenSSL's
+    AES-ECB keystream) is within the message's blocks of 2^32 with all ones above it, on either
+    side of a 1024-block row, for every key size; nonce lengths straddle the GHASH blocks."""
+    names = {c['name'] for c in CORNERS['cases']}
+    assert len(names) == len(CORNERS['cases'])
+    assert not names & {c['name'] for c in GCM['cases']}
+    for n in (17, 16385, 70_000):
+        for low in (0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFC00, 0xFFFFFBFF, 0xFFFFF000):
+            assert f'wrap_k32_iv16_c{low:08x}_p{n}' in names
+        for kb in (16, 24):
+            for low in (0xFFFFFFFF, 0xFFFFFBFF):
+                assert f'wrap_k{kb}_iv16_c{low:08x}_p{n}' in names
+        for ivn in (32, 128):
+            assert f'wrap_k32_iv{ivn}_cfffffbff_p{n}' in names
+    for c in CORNERS['cases']:
+        if c['name'].startswith('wrap_'):
+            low = int(c['name'].split('_c')[1][:8], 16)
+            assert int(c['j0'], 16) & 0xFFFFFFFFFFFFFFFF == 0xFFFFFFFF << 32 | low
+            assert len(bytes.fromhex(c['iv'])) == int(c['name'].split('_iv')[1].split('_')[0])
+    for ivn in (9, 15, 17, 31, 32, 33, 127):
+        for n in (17, 16385):
+            assert f'k32_iv{ivn}_p{n}' in names
 
 
 def test_decrypt_rejects_tampering(oracle):

@@ -2,7 +2,8 @@
 `aes_gcm` cipher adapter (replicat/utils/adapters.py:117-158) and the encrypted snapshot's
 per-chunk subkeys (repository.py:132-137, 1470-1473).
 
-Expected values: tests/golden/gcm.json (OpenSSL libcrypto, what `cryptography`'s AESGCM binds),
+Expected values: tests/golden/gcm.json and gcm_corners.json (OpenSSL libcrypto, what
+`cryptography`'s AESGCM binds; the corners are nonces solved so that inc32 wraps inside the message),
 the oracle (oracle/aesgcm_oracle.c, pinned by tests/test_gcm_oracle.py) and hashlib.blake2b for
 the subkeys.  Runs on an MI355X only (-m gpu)."""
 import hashlib
@@ -26,6 +27,7 @@ from replicat_amd.cipher import DecryptionError, GpuAesGcm  # noqa: E402
 from replicat_amd.hashing import SLOT, GpuBlake2b, state_init  # noqa: E402
 
 GCM = G.load('gcm.json')
+CORNERS = G.load('gcm_corners.json')
 
 
 def plaintext(case):
@@ -39,7 +41,7 @@ def dev(data):
     return torch.from_numpy(arr.copy()).cuda()
 
 
-@pytest.mark.parametrize('case', GCM['cases'], ids=lambda c: c['name'])
+@pytest.mark.parametrize('case', GCM['cases'] + CORNERS['cases'], ids=lambda c: c['name'])
 def test_openssl_fixture(case):
     key, iv, pt = bytes.fromhex(case['key']), bytes.fromhex(case['iv']), plaintext(case)
     g = GpuAesGcm(key_bits=8 * len(key), nonce_bits=8 * len(iv))
@@ -52,6 +54,26 @@ def test_openssl_fixture(case):
         assert hashlib.sha256(out).hexdigest() == case['out_sha256']
         assert out[-16:].hex() == case['tag']
     assert g.decrypt_many([blob], [key])[0] == pt
+
+
+@pytest.mark.parametrize('name', ['wrap_k32_iv16_cffffffff_p70000', 'wrap_k32_iv16_cfffffbff_p70000',
+                                  'wrap_k16_iv16_cfffffbff_p70000', 'wrap_k32_iv128_cfffffbff_p70000'])
+def test_tampering_after_the_counter_wrap(name):
+    """One ciphertext byte flipped in a block whose counter has already wrapped: InvalidTag (and
+    the untouched blob still decrypts)."""
+    case = next(c for c in CORNERS['cases'] if c['name'] == name)
+    key, iv, pt = bytes.fromhex(case['key']), bytes.fromhex(case['iv']), plaintext(case)
+    wrap_block = 0xFFFFFFFF - (int(case['j0'], 16) & 0xFFFFFFFF)  # its counter is 0
+    assert 16 * wrap_block + 21 < len(pt)
+    g = GpuAesGcm(key_bits=8 * len(key), nonce_bits=8 * len(iv))
+    blob = g.encrypt_many([pt], [key], [iv])[0]
+    assert hashlib.sha256(blob[len(iv):]).hexdigest() == case['out_sha256']
+    assert g.decrypt_many([blob], [key])[0] == pt
+    for pos in (16 * wrap_block, 16 * wrap_block + 21):
+        bad = bytearray(blob)
+        bad[len(iv) + pos] ^= 0x04
+        with pytest.raises(DecryptionError):
+            g.decrypt_many([bytes(bad)], [key])
 
 
 @pytest.mark.parametrize('kb', [16, 24, 32])
@@ -127,26 +149,39 @@ def test_device_buffers_unaligned(oracle):
     shifts = [1, 2, 3, 0, 1]
     ins = [dev(bytes(s) + d) for s, d in zip(shifts, datas)]
     kt, nt = dev(b''.join(keys)), dev(b''.join(nonces))
-    outs = [torch.zeros(3 + 12 + n + 16, dtype=torch.uint8, device='cuda') for n in lens]
+    # output i starts at byte 4 + shifts[i] of a tensor; 0xA5 around it shows a write out of place
+    outs = [torch.full((4 + 12 + n + 16 + 4,), 0xA5, dtype=torch.uint8, device='cuda') for n in lens]
+    oshift = [4 + s for s in shifts]  # the 12 nonce bytes keep that shift for the ciphertext
     g.encrypt_device([t.data_ptr() + s for t, s in zip(ins, shifts)], lens,
                      [kt.data_ptr() + 32 * i for i in range(len(lens))],
                      [nt.data_ptr() + 12 * i for i in range(len(lens))],
-                     [o.data_ptr() + 3 for o in outs], hs)
+                     [o.data_ptr() + s for o, s in zip(outs, oshift)], hs)
     torch.cuda.synchronize()
-    blobs = [o.cpu().numpy()[3:].tobytes() for o in outs]
+    blobs = []
+    for o, s, n in zip(outs, oshift, lens):
+        raw = o.cpu().numpy().tobytes()
+        blobs.append(raw[s:s + 28 + n])
+        assert raw[:s] == b'\xa5' * s and raw[s + 28 + n:] == b'\xa5' * (len(raw) - s - 28 - n)
     for d, k, v, b in zip(datas, keys, nonces, blobs):
         assert b == v + oracle.gcm_encrypt(k, v, d)
     blobs[3] = blobs[3][:40] + bytes([blobs[3][40] ^ 1]) + blobs[3][41:]
-    bins = [dev(b) for b in blobs]
-    pouts = [torch.zeros(max(n, 1), dtype=torch.uint8, device='cuda') for n in lens]
-    ok = torch.zeros(len(lens), dtype=torch.uint8, device='cuda')
-    g.decrypt_device([t.data_ptr() for t in bins], [len(b) for b in blobs],
+    bins = [dev(bytes(s) + b) for s, b in zip(shifts, blobs)]
+    pouts = [torch.full((4 + max(n, 1) + 4,), 0xA5, dtype=torch.uint8, device='cuda') for n in lens]
+    ok = torch.full((len(lens),), 7, dtype=torch.uint8, device='cuda')
+    g.decrypt_device([t.data_ptr() + s for t, s in zip(bins, shifts)], [len(b) for b in blobs],
                      [kt.data_ptr() + 32 * i for i in range(len(lens))],
-                     [p.data_ptr() for p in pouts], ok.data_ptr(), hs)
+                     [p.data_ptr() + s for p, s in zip(pouts, shifts)], ok.data_ptr(), hs)
     torch.cuda.synchronize()
     assert ok.cpu().tolist() == [1, 1, 1, 0, 1]
-    for i in (0, 1, 4):
-        assert pouts[i].cpu().numpy()[:lens[i]].tobytes() == datas[i]
+    for i in (0, 1, 2, 4):
+        raw = pouts[i].cpu().numpy().tobytes()
+        s, n = shifts[i], lens[i]
+        assert raw[s:s + n] == datas[i]
+        assert raw[:s] == b'\xa5' * s and raw[s + n:] == b'\xa5' * (len(raw) - s - n)
+    # the rejected blob may leave anything inside its own output, nothing around it
+    raw = pouts[3].cpu().numpy().tobytes()
+    s, n = shifts[3], lens[3]
+    assert raw[:s] == b'\xa5' * s and raw[s + n:] == b'\xa5' * (len(raw) - s - n)
 
 
 def test_many_small_messages(oracle):
@@ -158,15 +193,16 @@ def test_many_small_messages(oracle):
     nonces = [rnd.randbytes(12) for _ in range(n)]
     g = GpuAesGcm(key_bits=192)
     blobs = g.encrypt_many(datas, keys, nonces)
-    for i in range(0, n, 97):
-        assert blobs[i] == nonces[i] + oracle.gcm_encrypt(keys[i], nonces[i], datas[i])
+    for i in range(n):
+        assert blobs[i] == nonces[i] + oracle.gcm_encrypt(keys[i], nonces[i], datas[i]), i
     assert g.decrypt_many(blobs, keys) == datas
 
 
 @pytest.mark.parametrize('key_bits', [256, 128])
 def test_chunk_path(oracle, key_bits):
     """chunk -> digest -> derive_shared_subkey -> encrypt, all in HBM (repository.py:1454-1473),
-    against hashlib (digest, subkey) and the oracle (every blob)."""
+    against hashlib (digest, subkey) and the oracle (every blob); then the same call over counts
+    the test fills in itself: streams with a negative count contribute nothing."""
     rnd = random.Random(key_bits)
     mn, mx = 2_000, 80_000
     lens = [(3 << 20) - 7 * i for i in range(4)] + [0, 999]
@@ -217,3 +253,19 @@ def test_chunk_path(oracle, key_bits):
             s = e
             seen += 1
     assert seen == int(counts_h.sum()) > 100
+
+    # second call: the first four streams with counts [-3, 0, -1, <real>] over zeroed output
+    n4 = 4
+    counts2_h = np.array([-3, 0, -1, counts_h[3]], dtype=np.int64)
+    counts2 = torch.from_numpy(counts2_h).cuda()
+    out2 = torch.zeros(out_total, dtype=torch.uint8, device='cuda')
+    g.encrypt_chunks(ch, ptrs[:n4], lens[:n4], cuts.data_ptr(), counts2.data_ptr(), keys.data_ptr(),
+                     nonces.data_ptr(), out2.data_ptr(), hs)
+    torch.cuda.synchronize()
+    out2_h = out2.cpu().numpy()
+    _, base4 = g.chunks_layout(ch, lens[:n4])
+    assert [int(b) for b in base4] == [int(b) for b in base[:n4]]
+    lo = int(base[3])
+    hi = lo + lens[3] + 28 * int(counts_h[3])
+    assert not out2_h[:lo].any() and not out2_h[hi:].any()
+    assert np.array_equal(out2_h[lo:hi], out_h[lo:hi])
