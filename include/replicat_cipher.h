@@ -15,7 +15,8 @@
  * draws them from os.urandom, and so does the Python layer (replicat_amd/cipher.py).
  *
  * The per-chunk subkeys come from rc_blake2b_derive_chunks (replicat_digest.h).  Implemented by
- * replicat_amd/csrc/{capi_cipher.cpp,gcm.hip} in replicat_amd/libreplicat_chunker.so.
+ * replicat_amd/csrc/{capi_cipher.cpp,gcm.hip} in replicat_amd/libreplicat_chunker.so, over the
+ * host code both cipher families share (replicat_amd/csrc/cipher_host.cpp).
  */
 #ifndef REPLICAT_CIPHER_H
 #define REPLICAT_CIPHER_H
@@ -95,7 +96,7 @@ int rc_gcm_timing_read(rc_gcm *g, double *ms, uint64_t *calls);
  * counter 1, and T = Poly1305(pad16(C) || le64(0) || le64(len(C))).  The blob layout
  * nonce (12) || C || T (16) and every argument list are those of the rc_gcm_* twin; a message may
  * hold (2^32 - 1) * 64 bytes (the block counter), more is RC_ERR_ARGUMENT.  Implemented by
- * replicat_amd/csrc/{capi_chacha.cpp,chacha.hip}. */
+ * replicat_amd/csrc/{capi_chacha.cpp,chacha.hip} over the same cipher_host.cpp. */
 
 typedef struct rc_chacha rc_chacha;
 

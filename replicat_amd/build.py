@@ -21,7 +21,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libreplicat_chunker.so')
 SOURCES = [os.path.join(CSRC, n) for n in ('kernels.hip', 'capi.cpp', 'blake2b.hip', 'capi_digest.cpp', 'gcm.hip',
-                                             'capi_cipher.cpp', 'chacha.hip', 'capi_chacha.cpp')]
+                                             'capi_cipher.cpp', 'chacha.hip', 'capi_chacha.cpp', 'cipher_host.cpp')]
 HEADERS = [os.path.join(CSRC, n) for n in ('gclmul.h', 'digest_kernels.h', 'capi_internal.h', 'cipher_kernels.h',
                                              'knobs.h', 'diag.h', 'cipher_host.h', 'chacha_kernels.h',
                                              'poly1305_limbs.h')] + [

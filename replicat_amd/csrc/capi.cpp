@@ -93,63 +93,6 @@ uint64_t load_le64(const uint8_t *p) {
 
 uint64_t window_keys(uint64_t max_length) { return max_length >= 1 ? (max_length - 1) / 4 : 0; }
 
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-// growable device buffer
-struct DevBuf {
-    void *p = nullptr;
-    size_t n = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= n) return 0;
-        if (p) {
-            HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(hipFree(p));
-            p = nullptr;
-            n = 0;
-        }
-        size_t want = std::max<size_t>(bytes, 4096);
-        want = (want + 4095) & ~(size_t)4095;
-        HIP_TRY(hipMalloc(&p, want));
-        n = want;
-        return 0;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-struct HostBuf {  // growable pinned host buffer
-    void *p = nullptr;
-    size_t n = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= n) return 0;
-        if (p) HIP_TRY(hipHostFree(p));
-        p = nullptr;
-        n = 0;
-        size_t want = std::max<size_t>(bytes, 4096);
-        HIP_TRY(hipHostMalloc(&p, want, hipHostMallocDefault));
-        n = want;
-        return 0;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
 }  // namespace
 
 int rc_fail(int code, const char *fmt, ...) {
@@ -222,7 +165,7 @@ struct rc_chunker {
 
     // per-call workspaces, used alternately so that two calls can be in flight
     struct Workspace {
-        HostBuf h_desc;     // pinned staging of the descriptor arrays
+        PinnedBuf h_desc;     // pinned staging of the descriptor arrays
         DevBuf d_desc;      // device copy
         DevBuf d_records;   // one TileRecord per tile
         DevBuf d_scratch;   // speculative chain lists of multi-segment streams
@@ -240,7 +183,7 @@ struct rc_chunker {
 
     // single-buffer next_cut scratch
     DevBuf d_buf, d_out;
-    HostBuf h_out;
+    PinnedBuf h_out;
 
     // host-stream path scratch
     DevBuf d_stage[2], d_hcuts[2], d_hcounts[2], d_hdig[2];

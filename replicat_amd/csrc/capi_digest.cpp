@@ -19,83 +19,22 @@
 
 static_assert(sizeof(rc_blake2b_state) == 256, "rc_blake2b_state is a 256-byte device record");
 
-namespace {
-
-struct DevMem {
-    void *p = nullptr;
-    size_t n = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= n) return 0;
-        if (p) {
-            RC_HIP_TRY(hipDeviceSynchronize());
-            RC_HIP_TRY(hipFree(p));
-            p = nullptr;
-            n = 0;
-        }
-        const size_t want = (std::max<size_t>(bytes, 4096) + 4095) & ~size_t(4095);
-        RC_HIP_TRY(hipMalloc(&p, want));
-        n = want;
-        return 0;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-struct PinnedMem {
-    void *p = nullptr;
-    size_t n = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= n) return 0;
-        if (p) RC_HIP_TRY(hipHostFree(p));
-        p = nullptr;
-        n = 0;
-        RC_HIP_TRY(hipHostMalloc(&p, std::max<size_t>(bytes, 4096), hipHostMallocDefault));
-        n = std::max<size_t>(bytes, 4096);
-        return 0;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-struct Guard {
-    int prev = -1;
-    explicit Guard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~Guard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-}  // namespace
-
 struct rc_hasher {
     uint32_t digest_size = 64;
     int device = 0;
     rc::Knobs knobs;  // knobs.h, read once at creation (the lane / quad split)
     std::mutex mu;
     struct Workspace {
-        PinnedMem h_stage;   // host-built descriptors / items
-        DevMem d_stage;      // their device copy
-        DevMem d_items;      // work list of the chunk path
+        rc::PinnedBuf h_stage;   // host-built descriptors / items
+        rc::DevBuf d_stage;      // their device copy
+        rc::DevBuf d_items;      // work list of the chunk path
         hipEvent_t done = nullptr;
         bool pending = false;
     } ws[2];
     unsigned next_ws = 0;
     // blocking host path
-    DevMem d_data, d_out;
-    // timing
-    bool timing = false;
-    std::vector<hipEvent_t> ev_pool;
-    std::vector<std::array<hipEvent_t, 2>> ev_rec;
+    rc::DevBuf d_data, d_out;
+    rc::PairTimer timer;
 };
 
 namespace {
@@ -109,27 +48,6 @@ int acquire(rc_hasher *h, Workspace *&out) {
         w.pending = false;
     }
     out = &w;
-    return 0;
-}
-
-int timing_begin(rc_hasher *h, hipStream_t st, std::array<hipEvent_t, 2> &ev) {
-    if (!h->timing) return 0;
-    for (auto &e : ev) {
-        if (h->ev_pool.empty()) {
-            RC_HIP_TRY(hipEventCreate(&e));
-        } else {
-            e = h->ev_pool.back();
-            h->ev_pool.pop_back();
-        }
-    }
-    RC_HIP_TRY(hipEventRecord(ev[0], st));
-    return 0;
-}
-
-int timing_end(rc_hasher *h, hipStream_t st, std::array<hipEvent_t, 2> &ev) {
-    if (!h->timing) return 0;
-    RC_HIP_TRY(hipEventRecord(ev[1], st));
-    h->ev_rec.push_back(ev);
     return 0;
 }
 
@@ -153,8 +71,8 @@ int enqueue_items(rc_hasher *h, uint64_t n, const uint8_t *const *d_ptrs, const 
     // longest first: the kernel deals items round-robin (see blake2b.hip)
     std::stable_sort(it, it + n, [](const B2Item &x, const B2Item &y) { return x.len > y.len; });
     RC_HIP_TRY(hipMemcpyAsync(w->d_stage.p, w->h_stage.p, bytes, hipMemcpyHostToDevice, st));
-    std::array<hipEvent_t, 2> ev{};
-    if (int rc = timing_begin(h, st, ev)) return rc;
+    rc::PairTimer::Pair ev{};
+    if (int rc = h->timer.begin(st, ev)) return rc;
     uint64_t msg_bytes = 0;
     for (uint64_t i = 0; i < n; ++i) msg_bytes += lens[i];
     const uint64_t lane_max = rc_b2_lane_max(msg_bytes, it[0].len, h->knobs[rc::knB2LaneMax]);
@@ -162,7 +80,7 @@ int enqueue_items(rc_hasher *h, uint64_t n, const uint8_t *const *d_ptrs, const 
                            lane_max, rc_b2_lane_only(lane_max, it[0].len, h->knobs[rc::knB2LaneOnly] == 1),
                            st))
         return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
-    if (int rc = timing_end(h, st, ev)) return rc;
+    if (int rc = h->timer.end(st, ev)) return rc;
     return finish(h, *w, st);
 }
 
@@ -181,11 +99,11 @@ int enqueue_update(rc_hasher *h, uint64_t n, rc_blake2b_state *const *d_states,
                         reinterpret_cast<uint64_t>(d_states[i]), finals && finals[i] ? 1u : 0u, 0u};
     std::stable_sort(it, it + n, [](const B2UItem &x, const B2UItem &y) { return x.len > y.len; });
     RC_HIP_TRY(hipMemcpyAsync(w->d_stage.p, w->h_stage.p, bytes, hipMemcpyHostToDevice, st));
-    std::array<hipEvent_t, 2> ev{};
-    if (int rc = timing_begin(h, st, ev)) return rc;
+    rc::PairTimer::Pair ev{};
+    if (int rc = h->timer.begin(st, ev)) return rc;
     if (rc_b2_launch_update(static_cast<const B2UItem *>(w->d_stage.p), n, d_out, st))
         return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
-    if (int rc = timing_end(h, st, ev)) return rc;
+    if (int rc = h->timer.end(st, ev)) return rc;
     return finish(h, *w, st);
 }
 
@@ -205,7 +123,7 @@ int rc_hasher_enqueue_chunks(rc_hasher *h, uint64_t n, const uint8_t *const *d_p
                              uint64_t longest, uint8_t *d_out, hipStream_t st) {
     if (!n) return 0;
     std::lock_guard<std::mutex> lock(h->mu);
-    Guard g(h->device);
+    rc::DeviceGuard g(h->device);
     Workspace *w = nullptr;
     if (int rc = acquire(h, w)) return rc;
     // staging: ptr[n] cut_base[n] | device also: chunk_off[n+1], the sort histogram
@@ -222,8 +140,8 @@ int rc_hasher_enqueue_chunks(rc_hasher *h, uint64_t n, const uint8_t *const *d_p
     RC_HIP_TRY(hipMemcpyAsync(w->d_stage.p, w->h_stage.p, up, hipMemcpyHostToDevice, st));
     const uint64_t *d = static_cast<const uint64_t *>(w->d_stage.p);
     uint64_t *chunk_off = static_cast<uint64_t *>(w->d_stage.p) + 2 * n;
-    std::array<hipEvent_t, 2> ev{};
-    if (int rc = timing_begin(h, st, ev)) return rc;
+    rc::PairTimer::Pair ev{};
+    if (int rc = h->timer.begin(st, ev)) return rc;
     uint32_t *hist = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(w->d_stage.p) + hist_off);
     const uint64_t lane_max = rc_b2_lane_max(bytes, longest, h->knobs[rc::knB2LaneMax]);
     if (rc_b2_launch_chunks(n, d, d + n, d_cuts, d_counts, chunk_off, hist,
@@ -231,7 +149,7 @@ int rc_hasher_enqueue_chunks(rc_hasher *h, uint64_t n, const uint8_t *const *d_p
                             lane_max, rc_b2_lane_only(lane_max, longest, h->knobs[rc::knB2LaneOnly] == 1),
                             st))
         return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
-    if (int rc = timing_end(h, st, ev)) return rc;
+    if (int rc = h->timer.end(st, ev)) return rc;
     return finish(h, *w, st);
 }
 
@@ -252,7 +170,7 @@ int rc_blake2b_create(uint32_t digest_size, int device, rc_hasher **out) {
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
         return rc_fail(RC_ERR_NO_DEVICE, "no HIP device %d", device);
-    Guard g(device);
+    rc::DeviceGuard g(device);
     rc_hasher *h = new rc_hasher;
     h->knobs = knobs;
     h->digest_size = digest_size;
@@ -276,7 +194,7 @@ void rc_blake2b_destroy(rc_hasher *h) {
         // a call still running on another thread (a daemon thread when the exit hook runs)
         // finishes first: its buffers and streams go only after it
         std::lock_guard<std::mutex> lock(h->mu);
-        Guard g(h->device);
+        rc::DeviceGuard g(h->device);
         (void)hipDeviceSynchronize();
         for (auto &w : h->ws) {
             w.h_stage.release();
@@ -286,9 +204,7 @@ void rc_blake2b_destroy(rc_hasher *h) {
         }
         h->d_data.release();
         h->d_out.release();
-        for (auto &r : h->ev_rec)
-            for (auto e : r) (void)hipEventDestroy(e);
-        for (auto e : h->ev_pool) (void)hipEventDestroy(e);
+        h->timer.release();
     }
     delete h;
 }
@@ -302,7 +218,7 @@ int rc_blake2b_device(rc_hasher *h, uint64_t n, const uint8_t *const *d_ptrs, co
     if (!d_out) return rc_fail(RC_ERR_ARGUMENT, "null output");
     if (int rc = check_buffers(n, d_ptrs, lens)) return rc;
     std::lock_guard<std::mutex> lock(h->mu);
-    Guard g(h->device);
+    rc::DeviceGuard g(h->device);
     return enqueue_items(h, n, d_ptrs, lens, d_out, static_cast<hipStream_t>(hip_stream));
 }
 
@@ -313,7 +229,7 @@ int rc_blake2b_host(rc_hasher *h, uint64_t n, const uint8_t *const *ptrs, const 
     if (!out) return rc_fail(RC_ERR_ARGUMENT, "null output");
     if (int rc = check_buffers(n, ptrs, lens)) return rc;
     std::lock_guard<std::mutex> lock(h->mu);
-    Guard g(h->device);
+    rc::DeviceGuard g(h->device);
     std::vector<uint64_t> off(n);
     uint64_t total = 0;
     for (uint64_t i = 0; i < n; ++i) {
@@ -412,7 +328,7 @@ int rc_blake2b_update_device(rc_hasher *h, uint64_t n, rc_blake2b_state *const *
     }
     if (any_final && !d_out) return rc_fail(RC_ERR_ARGUMENT, "null output");
     std::lock_guard<std::mutex> lock(h->mu);
-    Guard g(h->device);
+    rc::DeviceGuard g(h->device);
     return enqueue_update(h, n, d_states, d_ptrs, lens, finals, d_out,
                           static_cast<hipStream_t>(hip_stream));
 }
@@ -431,7 +347,7 @@ int rc_blake2b_derive_chunks(rc_hasher *h, const rc_chunker *layout, uint64_t n,
     std::vector<uint64_t> caps(n);
     rc_cut_capacity(layout, n, lens, caps.data());
     std::lock_guard<std::mutex> lock(h->mu);
-    Guard g(h->device);
+    rc::DeviceGuard g(h->device);
     const hipStream_t st = static_cast<hipStream_t>(hip_stream);
     Workspace *w = nullptr;
     if (int rc = acquire(h, w)) return rc;
@@ -445,37 +361,26 @@ int rc_blake2b_derive_chunks(rc_hasher *h, const rc_chunker *layout, uint64_t n,
         acc += caps[i];
     }
     RC_HIP_TRY(hipMemcpyAsync(w->d_stage.p, u, bytes, hipMemcpyHostToDevice, st));
-    std::array<hipEvent_t, 2> ev{};
-    if (int rc = timing_begin(h, st, ev)) return rc;
+    rc::PairTimer::Pair ev{};
+    if (int rc = h->timer.begin(st, ev)) return rc;
     if (rc_b2_launch_derive(n, static_cast<const uint64_t *>(w->d_stage.p), d_counts, d_kdf_state,
                             d_digests, msg_len, d_keys, st))
         return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
-    if (int rc = timing_end(h, st, ev)) return rc;
+    if (int rc = h->timer.end(st, ev)) return rc;
     return finish(h, *w, st);
 }
 
 int rc_blake2b_timing_enable(rc_hasher *h, int enable) {
     if (!h) return rc_fail(RC_ERR_ARGUMENT, "null hasher");
-    h->timing = enable != 0;
+    h->timer.enabled = enable != 0;
     return RC_OK;
 }
 
 int rc_blake2b_timing_read(rc_hasher *h, double *ms, uint64_t *calls) {
     if (!h) return rc_fail(RC_ERR_ARGUMENT, "null hasher");
     std::lock_guard<std::mutex> lock(h->mu);
-    Guard g(h->device);
-    double a = 0;
-    for (auto &r : h->ev_rec) {
-        RC_HIP_TRY(hipEventSynchronize(r[1]));
-        float x = 0;
-        RC_HIP_TRY(hipEventElapsedTime(&x, r[0], r[1]));
-        a += x;
-        for (auto e : r) h->ev_pool.push_back(e);
-    }
-    if (ms) *ms = a;
-    if (calls) *calls = h->ev_rec.size();
-    h->ev_rec.clear();
-    return RC_OK;
+    rc::DeviceGuard g(h->device);
+    return h->timer.read(ms, calls);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// chacha_kernels.h -- internal interface between chacha.hip (kernel) and capi_chacha.cpp.
+// chacha_kernels.h -- internal interface between chacha.hip (kernel) and capi_chacha.cpp (its
+// launcher; the work lists are built by cipher_host.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,4 +1,5 @@
-// cipher_kernels.h -- internal interface between gcm.hip (kernels) and capi_cipher.cpp.
+// cipher_kernels.h -- internal interface between gcm.hip (kernels) and its host side:
+// capi_cipher.cpp (the launcher, the tables) and cipher_host.cpp (the work lists, for both ciphers).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
