@@ -1,5 +1,5 @@
 /*
- * replicat_digest.h -- C ABI of the MI355X (gfx950) BLAKE2b chunk digests.
+ * replicat_digest.h -- C ABI of the MI355X (gfx950) chunk digests: BLAKE2b, SHA-2 and SHA-3.
  *
  * Replaces, for the snapshot path, the per-chunk `self.props.hash_digest(output_chunk)` of
  * /root/reference/replicat/repository.py:1462, i.e. replicat's default hashing adapter
@@ -17,7 +17,12 @@
  *
  * Digests live in 64-byte slots: the digest of message i (or of cut slot s) is the first
  * digest_size bytes of slot i (s); the rest of the slot is zero.  Implemented by
- * replicat_amd/csrc/{capi_digest.cpp,blake2b.hip} in replicat_amd/libreplicat_chunker.so.
+ * replicat_amd/csrc/{capi_digest.cpp,blake2b.hip,sha2.hip,sha3.hip} in
+ * replicat_amd/libreplicat_chunker.so.
+ *
+ * The `sha2` and `sha3` adapters (adapters.py:231-254) are hashers of the same handle type:
+ * rc_sha2_create / rc_sha3_create, then the rc_hash_* entry points.  The shared-subkey KDF
+ * (rc_blake2b_derive_chunks, rc_blake2b_state_init) is BLAKE2b whatever the hasher is.
  */
 #ifndef REPLICAT_DIGEST_H
 #define REPLICAT_DIGEST_H
@@ -37,6 +42,15 @@ extern "C" {
 #define RC_ERR_B2_PARAM 5   /* "maximum key length is 64 bytes" / "maximum salt length is 16 bytes"
                               / "maximum person length is 16 bytes": hashlib's ValueErrors */
 
+#define RC_ERR_DIGEST_BITS 9 /* "Invalid digest size": the ValueError of the `sha2` / `sha3`
+                                adapters for bits outside 224 / 256 / 384 / 512 */
+
+/* The algorithm of a hasher handle and of a state record (its `algo` word; BLAKE2b's is the
+ * reserved word that has always been 0, so existing records stay valid). */
+#define RC_HASH_BLAKE2B 0
+#define RC_HASH_SHA2 1
+#define RC_HASH_SHA3 2
+
 typedef struct rc_hasher rc_hasher;
 
 /* An incremental BLAKE2b in DEVICE memory (256 bytes, 16-byte aligned): chaining value, bytes
@@ -51,6 +65,63 @@ typedef struct rc_blake2b_state {
     uint32_t reserved0;
     uint64_t reserved[5];
 } rc_blake2b_state;
+
+/* An incremental SHA-224/256/384/512 in DEVICE memory: the same 256 bytes and 16-byte alignment
+ * as rc_blake2b_state, so arrays of states keep their stride.  Built on the host by
+ * rc_sha2_state_init, advanced by rc_hash_update_device on a `sha2` handle of the same bits. */
+typedef struct rc_sha2_state {
+    uint64_t h[8];        /* chaining value; SHA-224/256: the eight 32-bit words, zero-extended */
+    uint64_t t;           /* bytes compressed: a multiple of the block (64, or 128 for 384/512) */
+    uint64_t buflen;      /* pending bytes in buf, 0..block-1 */
+    uint8_t buf[128];     /* the pending bytes; zero at and past buflen (SHA-224/256 use 64) */
+    uint32_t digest_size; /* 28 / 32 / 48 / 64 */
+    uint32_t algo;        /* RC_HASH_SHA2 */
+    uint64_t reserved[5];
+} rc_sha2_state;
+
+/* An incremental SHA3-224/256/384/512 in DEVICE memory (256 bytes, 16-byte aligned): the Keccak
+ * state with every message byte so far XORed in, and the absorb position. */
+typedef struct rc_sha3_state {
+    uint64_t a[25];       /* lanes a[x + 5 y], little-endian as FIPS 202 orders the bytes */
+    uint32_t pos;         /* bytes absorbed into the current block, 0..rate-1 */
+    uint32_t rate;        /* 200 - 2 * digest_size: 144 / 136 / 104 / 72 */
+    uint32_t digest_size; /* 28 / 32 / 48 / 64 (the offset of rc_blake2b_state's) */
+    uint32_t algo;        /* RC_HASH_SHA3 */
+    uint64_t reserved[5];
+} rc_sha3_state;
+
+/* `sha2(bits)` / `sha3(bits)` (adapters.py:231-254: hashlib.sha224 .. sha512, sha3_224 ..
+ * sha3_512) bound to HIP device `device`.  bits outside 224 / 256 / 384 / 512 fail with
+ * RC_ERR_DIGEST_BITS before any device is looked for.  The handle is an rc_hasher: every
+ * rc_hash_* entry below (and its rc_blake2b_* spelling) dispatches on the handle's algorithm. */
+int rc_sha2_create(uint32_t bits, int device, rc_hasher **out);
+int rc_sha3_create(uint32_t bits, int device, rc_hasher **out);
+
+/* hashlib.sha*() before any data as a state record: host-only, no device work. */
+int rc_sha2_state_init(uint32_t bits, rc_sha2_state *out);
+int rc_sha3_state_init(uint32_t bits, rc_sha3_state *out);
+
+/* The algorithm-neutral names of the entry points documented below under their rc_blake2b_*
+ * spelling: the same functions, for a handle of any algorithm.  rc_hash_update_device takes
+ * states of the handle's algorithm (rc_blake2b_state / rc_sha2_state / rc_sha3_state; void
+ * pointers here).  A SHA handle reads the states' algo and digest_size words back before it
+ * launches (one synchronisation of hip_stream) and fails with RC_ERR_ARGUMENT when one does not
+ * match the handle; a BLAKE2b handle keeps its unsynchronised path and trusts the caller. */
+void rc_hash_destroy(rc_hasher *h);
+uint32_t rc_hash_digest_size(const rc_hasher *h);
+uint32_t rc_hash_algorithm(const rc_hasher *h);
+int rc_hash_device(rc_hasher *h, uint64_t n, const uint8_t *const *d_ptrs, const uint64_t *lens,
+                   uint8_t *d_out, void *hip_stream);
+int rc_hash_host(rc_hasher *h, uint64_t n, const uint8_t *const *ptrs, const uint64_t *lens,
+                 uint8_t *out);
+int rc_hash_chunks(rc_hasher *h, const rc_chunker *layout, uint64_t n,
+                   const uint8_t *const *d_streams, const uint64_t *lens, const uint64_t *d_cuts,
+                   const int64_t *d_counts, uint8_t *d_digests, void *hip_stream);
+int rc_hash_update_device(rc_hasher *h, uint64_t n, void *const *d_states,
+                          const uint8_t *const *d_ptrs, const uint64_t *lens,
+                          const uint8_t *finals, uint8_t *d_out, void *hip_stream);
+int rc_hash_timing_enable(rc_hasher *h, int enable);
+int rc_hash_timing_read(rc_hasher *h, double *ms, uint64_t *calls);
 
 /* `blake2b(length=digest_size)` (adapters.py:196-197) bound to HIP device `device`. */
 int rc_blake2b_create(uint32_t digest_size, int device, rc_hasher **out);

@@ -21,6 +21,7 @@ RC_ERR_B2_PARAM = 5
 RC_ERR_KEY_SIZE = 6
 RC_ERR_NONCE_SIZE = 7
 RC_ERR_TAG = 8
+RC_ERR_DIGEST_BITS = 9
 RC_ERR_ARGUMENT = 10
 RC_ERR_ALIGN = 11
 RC_ERR_HIP = 12
@@ -33,6 +34,7 @@ RC_OPEN = 1
 RC_PIPELINED = 2
 RC_PIPELINE_END = 4
 RC_DIGEST_SLOT = 64
+RC_HASH_BLAKE2B, RC_HASH_SHA2, RC_HASH_SHA3 = 0, 1, 2
 
 # every symbol include/replicat_chunker.h, replicat_digest.h and replicat_cipher.h declare:
 # name -> (restype, argtypes)
@@ -87,6 +89,19 @@ SIGNATURES = {
     'rc_blake2b_timing_enable': (_int, [_p, _int]),
     'rc_blake2b_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
     'rc_blake2b_derive_chunks': (_int, [_p, _p, _u64, _p, _p, _p, _p, _u32, _p, _p]),
+    'rc_sha2_create': (_int, [_u32, _int, ctypes.POINTER(_p)]),
+    'rc_sha3_create': (_int, [_u32, _int, ctypes.POINTER(_p)]),
+    'rc_sha2_state_init': (_int, [_u32, _p]),
+    'rc_sha3_state_init': (_int, [_u32, _p]),
+    'rc_hash_destroy': (None, [_p]),
+    'rc_hash_digest_size': (_u32, [_p]),
+    'rc_hash_algorithm': (_u32, [_p]),
+    'rc_hash_device': (_int, [_p, _u64, _p, _p, _p, _p]),
+    'rc_hash_host': (_int, [_p, _u64, _p, _p, _p]),
+    'rc_hash_chunks': (_int, [_p, _p, _u64, _p, _p, _p, _p, _p, _p]),
+    'rc_hash_update_device': (_int, [_p, _u64, _p, _p, _p, _p, _p, _p]),
+    'rc_hash_timing_enable': (_int, [_p, _int]),
+    'rc_hash_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
     # replicat_cipher.h
     'rc_gcm_create': (_int, [_u32, _u32, _int, ctypes.POINTER(_p)]),
     'rc_gcm_destroy': (None, [_p]),
@@ -183,7 +198,7 @@ def check(code):
         return
     msg = last_error()
     if code in (RC_ERR_KEY_LENGTH, RC_ERR_MIN_GT_MAX, RC_ERR_BAD_KEY, RC_ERR_DIGEST_SIZE,
-                RC_ERR_B2_PARAM, RC_ERR_KEY_SIZE, RC_ERR_NONCE_SIZE):
+                RC_ERR_B2_PARAM, RC_ERR_KEY_SIZE, RC_ERR_NONCE_SIZE, RC_ERR_DIGEST_BITS):
         raise ValueError(msg)
     if code == RC_ERR_NO_DEVICE:
         raise ChunkerUnavailable(msg)

@@ -783,10 +783,9 @@ int rc_b2_launch_items(const B2Item *d_items, uint64_t n, uint32_t outlen, uint8
     return b2_status("rc_b2_kernel");
 }
 
-int rc_b2_launch_chunks(uint64_t n, const uint64_t *d_ptrs, const uint64_t *d_cut_base,
-                        const uint64_t *d_cuts, const int64_t *d_counts, uint64_t *d_chunk_off,
-                        uint32_t *d_hist, B2Item *d_items, uint64_t items_cap, uint32_t outlen,
-                        uint8_t *d_out, uint64_t lane_max, bool lane_only, hipStream_t stream) {
+int rc_b2_launch_sort(uint64_t n, const uint64_t *d_ptrs, const uint64_t *d_cut_base,
+                      const uint64_t *d_cuts, const int64_t *d_counts, uint64_t *d_chunk_off,
+                      uint32_t *d_hist, B2Item *d_items, hipStream_t stream) {
     if (!n) return 0;
     rc_b2_scan_kernel<<<1, 1024, 0, stream>>>(d_counts, n, d_chunk_off);
     if (b2_status("rc_b2_scan_kernel")) return 1;
@@ -797,7 +796,16 @@ int rc_b2_launch_chunks(uint64_t n, const uint64_t *d_ptrs, const uint64_t *d_cu
     rc_b2_hscan_kernel<<<1, 1024, 0, stream>>>(d_hist, uint64_t(kB2Buckets) * groups);
     if (b2_status("rc_b2_hscan_kernel")) return 1;
     rc_b2_scatter_kernel<<<groups, 256, 0, stream>>>(c, d_hist, d_items);
-    if (b2_status("rc_b2_scatter_kernel")) return 1;
+    return b2_status("rc_b2_scatter_kernel");
+}
+
+int rc_b2_launch_chunks(uint64_t n, const uint64_t *d_ptrs, const uint64_t *d_cut_base,
+                        const uint64_t *d_cuts, const int64_t *d_counts, uint64_t *d_chunk_off,
+                        uint32_t *d_hist, B2Item *d_items, uint64_t items_cap, uint32_t outlen,
+                        uint8_t *d_out, uint64_t lane_max, bool lane_only, hipStream_t stream) {
+    if (!n) return 0;
+    if (rc_b2_launch_sort(n, d_ptrs, d_cut_base, d_cuts, d_counts, d_chunk_off, d_hist, d_items, stream))
+        return 1;
     if (lane_only) {
         rc_b2_lane_kernel<<<b2_lane_only_grid(items_cap), kB2Threads, 0, stream>>>(
             d_items, d_chunk_off + n, 0, outlen, d_out);

@@ -1,4 +1,7 @@
-// capi_digest.cpp -- host side of include/replicat_digest.h: BLAKE2b digests on the device.
+// capi_digest.cpp -- host side of include/replicat_digest.h: BLAKE2b, SHA-2 and SHA-3 digests
+// on the device.  One handle type serves the three hashing adapters: the handle carries its
+// algorithm, and the three places that launch a digest kernel (enqueue_items, enqueue_update,
+// rc_hasher_enqueue_chunks) dispatch on it; everything around them is shared.
 //
 // The hasher mirrors replicat's `blake2b(length)` hashing adapter (replicat/utils/adapters.py
 // :195-225): its digest_size, and `digest(data)` = hashlib.blake2b(data, digest_size).digest()
@@ -16,10 +19,12 @@
 #include "capi_internal.h"
 #include "knobs.h"
 #include "digest_kernels.h"
+#include "sha_kernels.h"
 
 static_assert(sizeof(rc_blake2b_state) == 256, "rc_blake2b_state is a 256-byte device record");
 
 struct rc_hasher {
+    uint32_t algo = RC_HASH_BLAKE2B;
     uint32_t digest_size = 64;
     int device = 0;
     rc::Knobs knobs;  // knobs.h, read once at creation (the lane / quad split)
@@ -28,6 +33,8 @@ struct rc_hasher {
         rc::PinnedBuf h_stage;   // host-built descriptors / items
         rc::DevBuf d_stage;      // their device copy
         rc::DevBuf d_items;      // work list of the chunk path
+        rc::DevBuf d_tags;       // SHA updates: the states' algorithm words ..
+        rc::PinnedBuf h_tags;    // .. and their host copy
         hipEvent_t done = nullptr;
         bool pending = false;
     } ws[2];
@@ -75,11 +82,21 @@ int enqueue_items(rc_hasher *h, uint64_t n, const uint8_t *const *d_ptrs, const 
     if (int rc = h->timer.begin(st, ev)) return rc;
     uint64_t msg_bytes = 0;
     for (uint64_t i = 0; i < n; ++i) msg_bytes += lens[i];
-    const uint64_t lane_max = rc_b2_lane_max(msg_bytes, it[0].len, h->knobs[rc::knB2LaneMax]);
-    if (rc_b2_launch_items(static_cast<const B2Item *>(w->d_stage.p), n, h->digest_size, d_out,
-                           lane_max, rc_b2_lane_only(lane_max, it[0].len, h->knobs[rc::knB2LaneOnly] == 1),
-                           st))
-        return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
+    const B2Item *d_items = static_cast<const B2Item *>(w->d_stage.p);
+    if (h->algo == RC_HASH_SHA2) {
+        if (rc_sha2_launch_items(d_items, nullptr, n, n, h->digest_size, d_out,
+                                 rc_sha_lane_max(h->algo, msg_bytes, it[0].len, h->knobs[rc::knShaLaneMax]), st))
+            return rc_fail(RC_ERR_HIP, "%s", rc_sha_launch_error());
+    } else if (h->algo == RC_HASH_SHA3) {
+        if (rc_sha3_launch_items(d_items, nullptr, n, n, h->digest_size, d_out,
+                                 rc_sha_lane_max(h->algo, msg_bytes, it[0].len, h->knobs[rc::knShaLaneMax]), st))
+            return rc_fail(RC_ERR_HIP, "%s", rc_sha_launch_error());
+    } else {
+        const uint64_t lane_max = rc_b2_lane_max(msg_bytes, it[0].len, h->knobs[rc::knB2LaneMax]);
+        if (rc_b2_launch_items(d_items, n, h->digest_size, d_out, lane_max,
+                               rc_b2_lane_only(lane_max, it[0].len, h->knobs[rc::knB2LaneOnly] == 1), st))
+            return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
+    }
     if (int rc = h->timer.end(st, ev)) return rc;
     return finish(h, *w, st);
 }
@@ -99,10 +116,35 @@ int enqueue_update(rc_hasher *h, uint64_t n, rc_blake2b_state *const *d_states,
                         reinterpret_cast<uint64_t>(d_states[i]), finals && finals[i] ? 1u : 0u, 0u};
     std::stable_sort(it, it + n, [](const B2UItem &x, const B2UItem &y) { return x.len > y.len; });
     RC_HIP_TRY(hipMemcpyAsync(w->d_stage.p, w->h_stage.p, bytes, hipMemcpyHostToDevice, st));
+    const B2UItem *d_items = static_cast<const B2UItem *>(w->d_stage.p);
+    if (h->algo != RC_HASH_BLAKE2B) {
+        // a SHA kernel walking a record of another layout would read a wild pending count:
+        // read the records' algorithm words back first
+        const size_t tb = 2 * n * sizeof(uint32_t);
+        if (int rc = w->d_tags.ensure(tb)) return rc;
+        if (int rc = w->h_tags.ensure(tb)) return rc;
+        if (rc_sha_launch_tags(d_items, n, static_cast<uint32_t *>(w->d_tags.p), st))
+            return rc_fail(RC_ERR_HIP, "%s", rc_sha_launch_error());
+        RC_HIP_TRY(hipMemcpyAsync(w->h_tags.p, w->d_tags.p, tb, hipMemcpyDeviceToHost, st));
+        RC_HIP_TRY(hipStreamSynchronize(st));
+        const uint32_t *tg = static_cast<const uint32_t *>(w->h_tags.p);
+        for (uint64_t i = 0; i < n; ++i)
+            if (tg[2 * i] != h->digest_size || tg[2 * i + 1] != h->algo)
+                return rc_fail(RC_ERR_ARGUMENT, "a state (algorithm %u, digest_size %u) is not one of "
+                               "this hasher's (algorithm %u, digest_size %u)", tg[2 * i + 1], tg[2 * i],
+                               h->algo, h->digest_size);
+    }
     rc::PairTimer::Pair ev{};
     if (int rc = h->timer.begin(st, ev)) return rc;
-    if (rc_b2_launch_update(static_cast<const B2UItem *>(w->d_stage.p), n, d_out, st))
+    if (h->algo == RC_HASH_SHA2) {
+        if (rc_sha2_launch_update(d_items, n, h->digest_size, d_out, st))
+            return rc_fail(RC_ERR_HIP, "%s", rc_sha_launch_error());
+    } else if (h->algo == RC_HASH_SHA3) {
+        if (rc_sha3_launch_update(d_items, n, h->digest_size, d_out, st))
+            return rc_fail(RC_ERR_HIP, "%s", rc_sha_launch_error());
+    } else if (rc_b2_launch_update(d_items, n, d_out, st)) {
         return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
+    }
     if (int rc = h->timer.end(st, ev)) return rc;
     return finish(h, *w, st);
 }
@@ -143,12 +185,21 @@ int rc_hasher_enqueue_chunks(rc_hasher *h, uint64_t n, const uint8_t *const *d_p
     rc::PairTimer::Pair ev{};
     if (int rc = h->timer.begin(st, ev)) return rc;
     uint32_t *hist = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(w->d_stage.p) + hist_off);
-    const uint64_t lane_max = rc_b2_lane_max(bytes, longest, h->knobs[rc::knB2LaneMax]);
-    if (rc_b2_launch_chunks(n, d, d + n, d_cuts, d_counts, chunk_off, hist,
-                            static_cast<B2Item *>(w->d_items.p), total_cap, h->digest_size, d_out,
-                            lane_max, rc_b2_lane_only(lane_max, longest, h->knobs[rc::knB2LaneOnly] == 1),
-                            st))
-        return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
+    B2Item *items = static_cast<B2Item *>(w->d_items.p);
+    if (h->algo != RC_HASH_BLAKE2B) {  // the same longest-first list, then one lane per chunk
+        if (rc_b2_launch_sort(n, d, d + n, d_cuts, d_counts, chunk_off, hist, items, st))
+            return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
+        const uint64_t lane_max = rc_sha_lane_max(h->algo, bytes, longest, h->knobs[rc::knShaLaneMax]);
+        const int bad = (h->algo == RC_HASH_SHA2 ? rc_sha2_launch_items : rc_sha3_launch_items)(
+            items, chunk_off + n, 0, total_cap, h->digest_size, d_out, lane_max, st);
+        if (bad) return rc_fail(RC_ERR_HIP, "%s", rc_sha_launch_error());
+    } else {
+        const uint64_t lane_max = rc_b2_lane_max(bytes, longest, h->knobs[rc::knB2LaneMax]);
+        if (rc_b2_launch_chunks(n, d, d + n, d_cuts, d_counts, chunk_off, hist, items, total_cap,
+                                h->digest_size, d_out, lane_max,
+                                rc_b2_lane_only(lane_max, longest, h->knobs[rc::knB2LaneOnly] == 1), st))
+            return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
+    }
     if (int rc = h->timer.end(st, ev)) return rc;
     return finish(h, *w, st);
 }
@@ -157,13 +208,8 @@ namespace {
 thread_local char g_knob_err[256];
 }
 
-extern "C" {
-
-int rc_blake2b_create(uint32_t digest_size, int device, rc_hasher **out) {
-    if (!out) return rc_fail(RC_ERR_ARGUMENT, "null output handle");
-    *out = nullptr;
-    if (digest_size < 1 || digest_size > 64)
-        return rc_fail(RC_ERR_DIGEST_SIZE, "digest_size must be between 1 and 64 bytes");
+// the creation all three algorithms share, after their own argument check
+static int create_hasher(uint32_t algo, uint32_t digest_size, int device, rc_hasher **out) {
     rc::Knobs knobs;
     if (rc::read_knobs(knobs, g_knob_err, sizeof g_knob_err))
         return rc_fail(RC_ERR_ARGUMENT, "%s", g_knob_err);
@@ -173,6 +219,7 @@ int rc_blake2b_create(uint32_t digest_size, int device, rc_hasher **out) {
     rc::DeviceGuard g(device);
     rc_hasher *h = new rc_hasher;
     h->knobs = knobs;
+    h->algo = algo;
     h->digest_size = digest_size;
     h->device = device;
     for (auto &w : h->ws) {
@@ -185,6 +232,32 @@ int rc_blake2b_create(uint32_t digest_size, int device, rc_hasher **out) {
     rc_track(h, [](void *p) { rc_blake2b_destroy(static_cast<rc_hasher *>(p)); });
     *out = h;
     return RC_OK;
+}
+
+static bool sha_bits(uint32_t bits) { return bits == 224 || bits == 256 || bits == 384 || bits == 512; }
+
+extern "C" {
+
+int rc_blake2b_create(uint32_t digest_size, int device, rc_hasher **out) {
+    if (!out) return rc_fail(RC_ERR_ARGUMENT, "null output handle");
+    *out = nullptr;
+    if (digest_size < 1 || digest_size > 64)
+        return rc_fail(RC_ERR_DIGEST_SIZE, "digest_size must be between 1 and 64 bytes");
+    return create_hasher(RC_HASH_BLAKE2B, digest_size, device, out);
+}
+
+int rc_sha2_create(uint32_t bits, int device, rc_hasher **out) {
+    if (!out) return rc_fail(RC_ERR_ARGUMENT, "null output handle");
+    *out = nullptr;
+    if (!sha_bits(bits)) return rc_fail(RC_ERR_DIGEST_BITS, "Invalid digest size");
+    return create_hasher(RC_HASH_SHA2, bits / 8, device, out);
+}
+
+int rc_sha3_create(uint32_t bits, int device, rc_hasher **out) {
+    if (!out) return rc_fail(RC_ERR_ARGUMENT, "null output handle");
+    *out = nullptr;
+    if (!sha_bits(bits)) return rc_fail(RC_ERR_DIGEST_BITS, "Invalid digest size");
+    return create_hasher(RC_HASH_SHA3, bits / 8, device, out);
 }
 
 void rc_blake2b_destroy(rc_hasher *h) {
@@ -200,6 +273,8 @@ void rc_blake2b_destroy(rc_hasher *h) {
             w.h_stage.release();
             w.d_stage.release();
             w.d_items.release();
+            w.d_tags.release();
+            w.h_tags.release();
             if (w.done) (void)hipEventDestroy(w.done);
         }
         h->d_data.release();
@@ -210,6 +285,7 @@ void rc_blake2b_destroy(rc_hasher *h) {
 }
 
 uint32_t rc_blake2b_digest_size(const rc_hasher *h) { return h ? h->digest_size : 0; }
+uint32_t rc_hash_algorithm(const rc_hasher *h) { return h ? h->algo : 0; }
 
 int rc_blake2b_device(rc_hasher *h, uint64_t n, const uint8_t *const *d_ptrs, const uint64_t *lens,
                       uint8_t *d_out, void *hip_stream) {
@@ -341,6 +417,8 @@ int rc_blake2b_derive_chunks(rc_hasher *h, const rc_chunker *layout, uint64_t n,
     if (n == 0) return RC_OK;
     if (!lens || !d_counts || !d_kdf_state || !d_digests || !d_keys)
         return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    if (h->algo != RC_HASH_BLAKE2B)
+        return rc_fail(RC_ERR_ARGUMENT, "the shared-subkey KDF is BLAKE2b: pass a blake2b hasher");
     if (msg_len > kB2Slot) return rc_fail(RC_ERR_ARGUMENT, "msg_len above the 64-byte digest slot");
     if (reinterpret_cast<uintptr_t>(d_kdf_state) & 15)
         return rc_fail(RC_ERR_ARGUMENT, "KDF state not 16-byte aligned");
@@ -381,6 +459,66 @@ int rc_blake2b_timing_read(rc_hasher *h, double *ms, uint64_t *calls) {
     std::lock_guard<std::mutex> lock(h->mu);
     rc::DeviceGuard g(h->device);
     return h->timer.read(ms, calls);
+}
+
+int rc_sha2_state_init(uint32_t bits, rc_sha2_state *out) {
+    static const uint32_t iv224[8] = {0xc1059ed8u, 0x367cd507u, 0x3070dd17u, 0xf70e5939u,
+                                      0xffc00b31u, 0x68581511u, 0x64f98fa7u, 0xbefa4fa4u};
+    static const uint32_t iv256[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
+                                      0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+    static const uint64_t iv384[8] = {0xcbbb9d5dc1059ed8ull, 0x629a292a367cd507ull,
+                                      0x9159015a3070dd17ull, 0x152fecd8f70e5939ull,
+                                      0x67332667ffc00b31ull, 0x8eb44a8768581511ull,
+                                      0xdb0c2e0d64f98fa7ull, 0x47b5481dbefa4fa4ull};
+    static const uint64_t iv512[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull,
+                                      0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
+                                      0x510e527fade682d1ull, 0x9b05688c2b3e6c1full,
+                                      0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
+    if (!out) return rc_fail(RC_ERR_ARGUMENT, "null state");
+    if (!sha_bits(bits)) return rc_fail(RC_ERR_DIGEST_BITS, "Invalid digest size");
+    std::memset(out, 0, sizeof *out);
+    for (int i = 0; i < 8; ++i)
+        out->h[i] = bits == 224 ? iv224[i] : bits == 256 ? iv256[i] : bits == 384 ? iv384[i] : iv512[i];
+    out->digest_size = bits / 8;
+    out->algo = RC_HASH_SHA2;
+    return RC_OK;
+}
+
+int rc_sha3_state_init(uint32_t bits, rc_sha3_state *out) {
+    if (!out) return rc_fail(RC_ERR_ARGUMENT, "null state");
+    if (!sha_bits(bits)) return rc_fail(RC_ERR_DIGEST_BITS, "Invalid digest size");
+    std::memset(out, 0, sizeof *out);
+    out->rate = 200 - 2 * (bits / 8);
+    out->digest_size = bits / 8;
+    out->algo = RC_HASH_SHA3;
+    return RC_OK;
+}
+
+// the algorithm-neutral spellings
+void rc_hash_destroy(rc_hasher *h) { rc_blake2b_destroy(h); }
+uint32_t rc_hash_digest_size(const rc_hasher *h) { return rc_blake2b_digest_size(h); }
+int rc_hash_device(rc_hasher *h, uint64_t n, const uint8_t *const *d_ptrs, const uint64_t *lens,
+                   uint8_t *d_out, void *hip_stream) {
+    return rc_blake2b_device(h, n, d_ptrs, lens, d_out, hip_stream);
+}
+int rc_hash_host(rc_hasher *h, uint64_t n, const uint8_t *const *ptrs, const uint64_t *lens,
+                 uint8_t *out) {
+    return rc_blake2b_host(h, n, ptrs, lens, out);
+}
+int rc_hash_chunks(rc_hasher *h, const rc_chunker *layout, uint64_t n,
+                   const uint8_t *const *d_streams, const uint64_t *lens, const uint64_t *d_cuts,
+                   const int64_t *d_counts, uint8_t *d_digests, void *hip_stream) {
+    return rc_blake2b_chunks(h, layout, n, d_streams, lens, d_cuts, d_counts, d_digests, hip_stream);
+}
+int rc_hash_update_device(rc_hasher *h, uint64_t n, void *const *d_states,
+                          const uint8_t *const *d_ptrs, const uint64_t *lens,
+                          const uint8_t *finals, uint8_t *d_out, void *hip_stream) {
+    return rc_blake2b_update_device(h, n, reinterpret_cast<rc_blake2b_state *const *>(d_states), d_ptrs,
+                                    lens, finals, d_out, hip_stream);
+}
+int rc_hash_timing_enable(rc_hasher *h, int enable) { return rc_blake2b_timing_enable(h, enable); }
+int rc_hash_timing_read(rc_hasher *h, double *ms, uint64_t *calls) {
+    return rc_blake2b_timing_read(h, ms, calls);
 }
 
 }  // extern "C"

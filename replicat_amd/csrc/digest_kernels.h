@@ -44,6 +44,13 @@ inline uint64_t rc_b2_hist_words(uint64_t n) {
     return uint64_t(kB2Buckets) * ((n + spw - 1) / spw + 1);
 }
 
+// The longest-first work list of the chunks of n streams as rc_chunk_device wrote them (the
+// passes rc_b2_launch_chunks runs before its digest kernel): d_items gets sum-of-counts entries,
+// d_chunk_off[n] their number.  Every hasher's chunk path starts here (sha_kernels.h).
+int rc_b2_launch_sort(uint64_t n, const uint64_t *d_ptrs, const uint64_t *d_cut_base,
+                      const uint64_t *d_cuts, const int64_t *d_counts, uint64_t *d_chunk_off,
+                      uint32_t *d_hist, B2Item *d_items, hipStream_t stream);
+
 // Digests of the chunks of n streams as rc_chunk_device wrote them: d_cuts at d_cut_base[i],
 // d_counts[i] chunks.  d_chunk_off has n + 1 entries, d_hist rc_b2_hist_words(n); d_items holds
 // items_cap (>= sum of counts) entries.  The work list is sorted longest first on the device.

@@ -33,6 +33,7 @@ enum Knob : int {
     knRepair,         // RC_REPAIR
     knB2LaneMax,      // RC_B2_LANE_MAX
     knB2LaneOnly,     // RC_B2_LANE_ONLY
+    knShaLaneMax,     // RC_SHA_LANE_MAX
     knProbeBlock,     // RC_PROBE_BLOCK
     knGcmDebug,       // RC_GCM_DEBUG
     knTileStreams,    // RC_TILE_STREAMS
@@ -87,6 +88,9 @@ inline constexpr KnobSpec kKnobTable[kKnobCount] = {
     {"RC_B2_LANE_ONLY", 0, 0, 2, "auto|0|1",
      "BLAKE2b: 0 never uses the lane-only kernel (the fused kernel's lane role instead); "
      "auto and 1 use it when every message fits a lane"},
+    {"RC_SHA_LANE_MAX", -1, -1, int64_t(1) << 62, nullptr,
+     "SHA-2 / SHA-3: longest message hashed by one lane, longer ones by the latency form (SHA-2: "
+     "a wave per message, SHA-3: 25-lane groups); -1: the rule, 0: the latency form only"},
     {"RC_PROBE_BLOCK", 0, 0, int64_t(1) << 20, nullptr,
      "read probe: interleaved static runs of this many tiles (0: the tile kernel's schedule)"},
     {"RC_GCM_DEBUG", 0, 0, 1, "0|1",

@@ -1,4 +1,4 @@
-"""BLAKE2b chunk digests on the device.
+"""BLAKE2b, SHA-2 and SHA-3 chunk digests on the device.
 
 replicat's snapshot loop takes ``self.props.hash_digest(output_chunk)`` of every chunk it cuts
 (/root/reference/replicat/repository.py:1462).  The default hashing adapter is
@@ -24,9 +24,17 @@ and the incremental / keyed half of the adapter over device-resident states
 * ``DeviceIncrementalHasher`` -- ``incremental_hasher()`` (adapters.py:227-228) itself;
 * ``derive_chunks(...)`` -- the subkey of every chunk digest left in HBM (repository.py:1470-1472).
 
+``GpuSha2(bits=...)`` and ``GpuSha3(bits=...)`` are the ``sha2`` / ``sha3`` adapters
+(adapters.py:231-254: hashlib.sha224 .. sha512, sha3_224 .. sha3_512) with the same batch
+surface -- one class body (``_GpuHasher``) over a per-algorithm description -- and
+``hasher_from_config(name, **kwargs)`` maps a repository's ``hashing`` section to one of the
+three.  The shared-subkey KDF (``derive_chunks``) is BLAKE2b whatever the hasher is, so only
+``GpuBlake2b`` has it.
+
 There is no CPU fallback: without the HIP library every call raises.
 """
 import ctypes
+import hashlib
 
 import numpy as np
 
@@ -61,25 +69,47 @@ def state_init(digest_size: int = 64, *, key=b'', salt=b'', person=b'') -> bytes
     return out.raw
 
 
-class GpuBlake2b:
-    """``blake2b(length=...)`` (adapters.py:195-197) on one HIP device."""
+SHA_BITS = (224, 256, 384, 512)
 
-    def __init__(self, *, length: int = 64, device=None):
+
+def sha_state_init(name: str, bits: int = 512) -> bytes:
+    """hashlib.sha*() / sha3_*() before any data, as the 256-byte rc_sha2_state / rc_sha3_state
+    record (``name`` is 'sha2' or 'sha3').  Raises the adapters' ValueError('Invalid digest
+    size') for other bits."""
+    if name not in ('sha2', 'sha3'):
+        raise ValueError(f'unknown SHA family {name!r}')
+    if not isinstance(bits, int):
+        raise TypeError(f'{type(bits).__name__!r} object cannot be interpreted as an integer')
+    out = ctypes.create_string_buffer(STATE_BYTES)
+    fn = lib().rc_sha2_state_init if name == 'sha2' else lib().rc_sha3_state_init
+    check(fn(bits if 0 <= bits < 1 << 32 else 0, out))
+    return out.raw
+
+
+class _GpuHasher:
+    """The batch surface every hashing adapter shares, over one rc_hasher handle.  A subclass
+    sets ``name`` (the adapter's name in a repository's configuration) and creates the handle;
+    the entry points dispatch on the handle's algorithm inside the library."""
+
+    name = None
+
+    def _create(self, create, arg, size, device):
         if device is None:
             device = _current_device()
-        if not isinstance(length, int):
-            raise TypeError(f'{type(length).__name__!r} object cannot be interpreted as an integer')
         handle = ctypes.c_void_p()
-        check(lib().rc_blake2b_create(length if 0 <= length < 1 << 32 else 0, int(device),
-                                      ctypes.byref(handle)))
+        check(create(arg if 0 <= arg < 1 << 32 else 0, int(device), ctypes.byref(handle)))
         self._h = handle
-        self.digest_size = int(length)
+        self.digest_size = int(size)
         self.device = int(device)
+
+    def initial_state(self, *, key=b'', salt=b'', person=b'') -> bytes:
+        """The 256-byte state record of a fresh incremental hash of this adapter."""
+        raise NotImplementedError
 
     def close(self):
         h, self._h = getattr(self, '_h', None), None
         if h:
-            lib().rc_blake2b_destroy(h)
+            lib().rc_hash_destroy(h)
 
     def __del__(self):
         try:
@@ -102,8 +132,7 @@ class GpuBlake2b:
         lens = _ptr_array([a.size for a in arrs])
         ptrs = _ptr_array([a.ctypes.data if a.size else 0 for a in arrs])
         out = np.zeros((n, SLOT), dtype=np.uint8)
-        check(lib().rc_blake2b_host(self._h, n, ptrs.ctypes.data, lens.ctypes.data,
-                                    out.ctypes.data))
+        check(lib().rc_hash_host(self._h, n, ptrs.ctypes.data, lens.ctypes.data, out.ctypes.data))
         return [out[i, :self.digest_size].tobytes() for i in range(n)]
 
     # ---------------------------------------------------------------- device buffers
@@ -111,28 +140,52 @@ class GpuBlake2b:
     def digest_device(self, ptrs, lens, out_ptr, stream=0):
         """Enqueue the digests of device buffers (raw pointers) into 64-byte slots at out_ptr."""
         ptrs, lens = _ptr_array(ptrs), _ptr_array(lens)
-        check(lib().rc_blake2b_device(self._h, len(lens), ptrs.ctypes.data, lens.ctypes.data,
-                                      out_ptr, stream or None))
+        check(lib().rc_hash_device(self._h, len(lens), ptrs.ctypes.data, lens.ctypes.data,
+                                   out_ptr, stream or None))
 
     def digest_chunks(self, chunker, ptrs, lens, cuts_ptr, counts_ptr, out_ptr, stream=0):
         """Enqueue the digests of the chunks ``chunker.chunk_device`` wrote for these streams:
         the slot of cut s (``cuts_ptr`` layout, ``chunker.capacity(lens)``) is out + 64 s."""
         ptrs, lens = _ptr_array(ptrs), _ptr_array(lens)
-        check(lib().rc_blake2b_chunks(self._h, chunker._h, len(lens), ptrs.ctypes.data,
-                                      lens.ctypes.data, cuts_ptr, counts_ptr, out_ptr,
-                                      stream or None))
+        check(lib().rc_hash_chunks(self._h, chunker._h, len(lens), ptrs.ctypes.data,
+                                   lens.ctypes.data, cuts_ptr, counts_ptr, out_ptr,
+                                   stream or None))
 
     def update_device(self, state_ptrs, ptrs, lens, finals, out_ptr=0, stream=0):
-        """Enqueue incremental updates (rc_blake2b_update_device): item i feeds device buffer
+        """Enqueue incremental updates (rc_hash_update_device): item i feeds device buffer
         ptrs[i] into the device state state_ptrs[i]; finals[i] also writes its digest to
         out + 64 i (the state is then left as it was)."""
         states, ptrs, lens = _ptr_array(state_ptrs), _ptr_array(ptrs), _ptr_array(lens)
         fin = np.ascontiguousarray(np.asarray(finals, dtype=np.uint8).reshape(-1))
         if not (len(states) == len(ptrs) == len(lens) == len(fin)):
             raise ValueError('states, ptrs, lens and finals differ in length')
-        check(lib().rc_blake2b_update_device(self._h, len(lens), states.ctypes.data,
-                                             ptrs.ctypes.data, lens.ctypes.data,
-                                             fin.ctypes.data, out_ptr or None, stream or None))
+        check(lib().rc_hash_update_device(self._h, len(lens), states.ctypes.data,
+                                          ptrs.ctypes.data, lens.ctypes.data,
+                                          fin.ctypes.data, out_ptr or None, stream or None))
+
+    # ---------------------------------------------------------------------- profiling
+
+    def timing(self, enable: bool):
+        check(lib().rc_hash_timing_enable(self._h, 1 if enable else 0))
+
+    def read_timing(self):
+        ms, n = ctypes.c_double(), ctypes.c_uint64()
+        check(lib().rc_hash_timing_read(self._h, ctypes.byref(ms), ctypes.byref(n)))
+        return ms.value, n.value
+
+
+class GpuBlake2b(_GpuHasher):
+    """``blake2b(length=...)`` (adapters.py:195-197) on one HIP device."""
+
+    name = 'blake2b'
+
+    def __init__(self, *, length: int = 64, device=None):
+        if not isinstance(length, int):
+            raise TypeError(f'{type(length).__name__!r} object cannot be interpreted as an integer')
+        self._create(lib().rc_blake2b_create, length, length, device)
+
+    def initial_state(self, *, key=b'', salt=b'', person=b''):
+        return state_init(self.digest_size, key=key, salt=salt, person=person)
 
     def derive_chunks(self, chunker, lens, counts_ptr, kdf_state_ptr, digests_ptr, keys_ptr,
                       stream=0):
@@ -145,28 +198,71 @@ class GpuBlake2b:
                                              counts_ptr, kdf_state_ptr, digests_ptr,
                                              self.digest_size, keys_ptr, stream or None))
 
-    # ---------------------------------------------------------------------- profiling
 
-    def timing(self, enable: bool):
-        check(lib().rc_blake2b_timing_enable(self._h, 1 if enable else 0))
+class _GpuSha(_GpuHasher):
+    """``sha2(bits=...)`` / ``sha3(bits=...)`` (adapters.py:231-254) on one HIP device."""
 
-    def read_timing(self):
-        ms, n = ctypes.c_double(), ctypes.c_uint64()
-        check(lib().rc_blake2b_timing_read(self._h, ctypes.byref(ms), ctypes.byref(n)))
-        return ms.value, n.value
+    def __init__(self, *, bits: int = 512, device=None):
+        if not isinstance(bits, int):
+            raise TypeError(f'{type(bits).__name__!r} object cannot be interpreted as an integer')
+        if bits not in SHA_BITS:  # the adapters' own check, before any device call
+            raise ValueError('Invalid digest size')
+        create = lib().rc_sha2_create if self.name == 'sha2' else lib().rc_sha3_create
+        self._create(create, bits, bits // 8, device)
+        self.bits = bits
+
+    def initial_state(self, *, key=b'', salt=b'', person=b''):
+        if key or salt or person:
+            raise TypeError(f'{self.name} takes no key, salt or person')
+        return sha_state_init(self.name, self.bits)
+
+
+class GpuSha2(_GpuSha):
+    name = 'sha2'
+
+
+class GpuSha3(_GpuSha):
+    name = 'sha3'
+
+
+def hasher_from_config(name: str, **kwargs):
+    """The hasher of a repository's ``hashing`` section, with the names and arguments of
+    replicat's ``adapters.from_config``: 'blake2b' (``length=``), 'sha2' and 'sha3' (``bits=``);
+    ``device=`` is passed through."""
+    try:
+        cls = {'blake2b': GpuBlake2b, 'sha2': GpuSha2, 'sha3': GpuSha3}[name]
+    except (KeyError, TypeError):
+        raise ValueError(f'unknown hashing adapter {name!r}') from None
+    return cls(**kwargs)
+
+
+def initial_state_from_config(name: str, *, length: int = 64, bits: int = 512) -> bytes:
+    """The state record of a fresh incremental hash of that adapter (no device needed)."""
+    return state_init(length) if name == 'blake2b' else sha_state_init(name, bits)
+
+
+def hashlib_from_config(name: str, *, length: int = 64, bits: int = 512):
+    """The hashlib object that adapter wraps: what host threads use for long files."""
+    if name == 'blake2b':
+        return hashlib.blake2b(digest_size=length)
+    if name not in ('sha2', 'sha3') or bits not in SHA_BITS:
+        raise ValueError('Invalid digest size' if name in ('sha2', 'sha3') else
+                         f'unknown hashing adapter {name!r}')
+    return hashlib.new(('sha' if name == 'sha2' else 'sha3_') + str(bits))
 
 
 class DeviceIncrementalHasher:
-    """``blake2b(length).incremental_hasher()`` (adapters.py:227-228; HashlibIncrementalHasher
-    :106-114) with its state in HBM: ``feed(data)`` uploads and compresses on the device,
-    ``digest()`` finalises.  Optional key / salt / person as hashlib.blake2b takes them."""
+    """``incremental_hasher()`` of any of the three adapters (adapters.py:227-228;
+    HashlibIncrementalHasher :106-114) with its state in HBM: ``feed(data)`` uploads and
+    compresses on the device, ``digest()`` finalises.  Optional key / salt / person as
+    hashlib.blake2b takes them; a SHA hasher raises TypeError for them, as hashlib's sha
+    constructors do."""
 
-    def __init__(self, hasher: 'GpuBlake2b', *, key=b'', salt=b'', person=b''):
+    def __init__(self, hasher, *, key=b'', salt=b'', person=b''):
         import torch
         self._hasher = hasher
         dev = torch.device('cuda', hasher.device)
-        init = np.frombuffer(state_init(hasher.digest_size, key=key, salt=salt, person=person),
-                             dtype=np.uint8)
+        init = np.frombuffer(hasher.initial_state(key=key, salt=salt, person=person), dtype=np.uint8)
         self._state = torch.from_numpy(init.copy()).to(dev)
         self._slot = torch.zeros(SLOT, dtype=torch.uint8, device=dev)
         self._dev = dev
@@ -213,5 +309,6 @@ def chunk_digest_host(chunker, hasher, buffers, last_piece=None, open_=False):
             [digests[b:b + c, :hasher.digest_size] for b, c in zip(base, counts)])
 
 
-__all__ = ['GpuBlake2b', 'DeviceIncrementalHasher', 'chunk_digest_host', 'state_init', 'SLOT',
-           'STATE_BYTES']
+__all__ = ['GpuBlake2b', 'GpuSha2', 'GpuSha3', 'hasher_from_config', 'initial_state_from_config',
+           'hashlib_from_config', 'DeviceIncrementalHasher',
+           'chunk_digest_host', 'state_init', 'sha_state_init', 'SLOT', 'STATE_BYTES', 'SHA_BITS']

@@ -68,7 +68,8 @@ import numpy as np
 
 from .chunker import (MAX_LENGTH, MIN_LENGTH, GpuChunker, QueueStream, _current_device,
                       check_counts, normalize_params)
-from .hashing import SLOT, GpuBlake2b, state_init
+from .hashing import (SHA_BITS, SLOT, GpuBlake2b, hasher_from_config, hashlib_from_config,
+                      initial_state_from_config, state_init)
 from .snapshot import PIECE, PieceReader, file_parts, sort_files
 
 # The device time of a batch has a floor: the BLAKE2b chain of its longest chunk (~55 ms for a
@@ -312,8 +313,8 @@ class _Slot:
         dev = prod.dev
         # per-slot native handles: a handle's staging workspaces are reused every other call, so
         # a shared one would make the host wait for batch k's digests before queuing batch k + 2's
-        self.hasher = GpuBlake2b(length=prod.digest_size, device=prod.device)
-        self.file_hasher = GpuBlake2b(length=prod.digest_size, device=prod.device)
+        self.hasher = prod.make_hasher()
+        self.file_hasher = prod.make_hasher()
         self.host = torch.empty(prod.capacity, dtype=torch.uint8, pin_memory=True)
         self.hnp = self.host.numpy()
         self.dbuf = torch.empty(prod.capacity, dtype=torch.uint8, device=dev)
@@ -339,6 +340,7 @@ class _Slot:
             self.d_nonces = torch.empty(total * nb, dtype=torch.uint8, device=dev)
             self.d_enc = torch.empty(max(prod.enc_cap, 1), dtype=torch.uint8, device=dev)
             self.h_enc = torch.empty(max(prod.enc_cap, 1), dtype=torch.uint8, pin_memory=True)
+            # the shared-subkey KDF is BLAKE2b whatever the hasher is; it absorbs digest_size bytes
             self.kdf_hasher = GpuBlake2b(length=prod.digest_size, device=prod.device)
             self.cipher = prod.encryption.make_cipher(prod.device)
         self.lease = _Lease()  # stream(): records still viewing host / h_enc
@@ -370,11 +372,31 @@ class DeviceSnapshotProducer:
     stream on one HIP device."""
 
     def __init__(self, *, min_length: int = MIN_LENGTH, max_length: int = MAX_LENGTH,
-                 params: Optional[bytes] = None, digest_size: int = 64,
+                 params: Optional[bytes] = None, digest_size: Optional[int] = None,
                  batch_bytes: int = DEFAULT_BATCH, device=None, keep_contents: bool = True,
                  encryption: Optional[ChunkEncryption] = None, file_digests: str = 'auto',
                  slots: int = 3, queues: str = 'own', read_threads: int = 4,
-                 timeline: bool = False):
+                 timeline: bool = False, hashing: str = 'blake2b',
+                 hash_bits: Optional[int] = None):
+        # hashing / hash_bits: the repository's hashing adapter (adapters.from_config): 'blake2b'
+        # with digest_size (its `length`, default 64), or 'sha2' / 'sha3' with hash_bits (their
+        # `bits`, default 512), from which digest_size follows
+        if hashing == 'blake2b':
+            if hash_bits is not None:
+                raise ValueError('hash_bits belongs to sha2 / sha3; blake2b takes digest_size')
+            digest_size = 64 if digest_size is None else digest_size
+            self._hash_args = {'length': digest_size}
+        elif hashing in ('sha2', 'sha3'):
+            hash_bits = 512 if hash_bits is None else hash_bits
+            if hash_bits not in SHA_BITS:
+                raise ValueError('Invalid digest size')
+            if digest_size is not None and digest_size != hash_bits // 8:
+                raise ValueError(f'digest_size {digest_size} disagrees with hash_bits {hash_bits}')
+            digest_size = hash_bits // 8
+            self._hash_args = {'bits': hash_bits}
+        else:
+            raise ValueError(f'hashing must be blake2b, sha2 or sha3, not {hashing!r}')
+        self.hashing, self.hash_bits = hashing, hash_bits
         import torch
         if device is None:
             device = _current_device()
@@ -410,7 +432,9 @@ class DeviceSnapshotProducer:
         self.head = (max_length + 127) // 64 * 64
         self.capacity = self.head + self.batch_bytes + PIECE + 64
         self.cut_cap, _ = self.chunker.capacity([self.capacity])
-        self._init_state = np.frombuffer(state_init(digest_size), dtype=np.uint8)
+        self._init_state = np.frombuffer(initial_state_from_config(hashing, **self._hash_args),
+                                         dtype=np.uint8)
+        self.HOST_DIGEST_MIN = self.HOST_DIGEST_MIN_BY_HASH[hashing, hash_bits]
         self.encryption = encryption
         if encryption is not None:
             # the layout of the ciphertexts (nonce || C || T per chunk); each slot encrypts with
@@ -435,6 +459,20 @@ class DeviceSnapshotProducer:
     # HOST_DIGEST_MIN bytes on host threads, piece by piece as they are read, overlapped with
     # the reads and the device work; 'device' and 'host' force one engine.
     HOST_DIGEST_MIN = 1 << 20
+    # A SHA file digest is one lane's chain (sha_walk.h: incremental updates run the lane form),
+    # slower per byte than BLAKE2b's quad, so its threshold is lower: a file's device chain may be
+    # no longer than BLAKE2b's at 1 MiB, i.e. 1 MiB x (BLAKE2b's time / that hasher's time for the
+    # same chain), rounded down to a power of two.  The times are those of a 1 GiB batch of
+    # config 2's chunks, which its longest chunk's chain bounds and which repeats within 1-2 %
+    # (scripts/sha_probe.py, profiles/sha/sha_probe.json "config2_1gib", SHA-3 in the lane form;
+    # DESIGN.md §3f): blake2b 53.5 ms, sha2-256 218.0, sha2-512 316.7, sha3-224 336.1, sha3-256
+    # 355.1, sha3-384 462.0, sha3-512 654.1.  sha2-224 and sha2-384 run the 256 and 512 cores.
+    # 1 MiB x 53.5 / ms: 257,242  177,023  166,837  157,878  121,373  85,720 bytes.
+    HOST_DIGEST_MIN_BY_HASH = {
+        ('blake2b', None): 1 << 20,
+        ('sha2', 224): 1 << 17, ('sha2', 256): 1 << 17, ('sha2', 384): 1 << 17, ('sha2', 512): 1 << 17,
+        ('sha3', 224): 1 << 17, ('sha3', 256): 1 << 17, ('sha3', 384): 1 << 16, ('sha3', 512): 1 << 16,
+    }
 
     def _on_host(self, fi, f, hstates, engine):
         """Whether file fi's digest runs on a host thread; decided once per file (its bytes must
@@ -447,9 +485,12 @@ class DeviceSnapshotProducer:
             else:
                 engine[fi] = self.file_digests == 'host'
             if engine[fi]:
-                import hashlib
-                hstates[fi] = _HostHash(hashlib.blake2b(digest_size=self.digest_size))
+                hstates[fi] = _HostHash(hashlib_from_config(self.hashing, **self._hash_args))
         return engine[fi]
+
+    def make_hasher(self):
+        """A hasher handle of the repository's hashing adapter on the producer's device."""
+        return hasher_from_config(self.hashing, device=self.device, **self._hash_args)
 
     def close(self):
         """Release the pinned batches, their device copies and the host threads (the object is
