@@ -28,6 +28,7 @@ RC_ERR_HIP = 12
 RC_ERR_OVERFLOW = 13
 RC_ERR_NO_DEVICE = 14
 RC_ERR_DEVICE_FAULT = 15
+RC_ERR_CORRUPT = 16
 RC_COUNT_OVERFLOW = -1  # rc_chunk_device's per-stream counts besides the cut count
 RC_COUNT_FAULT = -3
 RC_OPEN = 1
@@ -35,8 +36,11 @@ RC_PIPELINED = 2
 RC_PIPELINE_END = 4
 RC_DIGEST_SLOT = 64
 RC_HASH_BLAKE2B, RC_HASH_SHA2, RC_HASH_SHA3 = 0, 1, 2
+RC_CIPHER_NONE, RC_CIPHER_AES_GCM, RC_CIPHER_CHACHA20_POLY1305 = 0, 1, 2
+RC_CHUNK_OK, RC_CHUNK_BAD_TAG, RC_CHUNK_CORRUPT = 0, 1, 2
 
-# every symbol include/replicat_chunker.h, replicat_digest.h and replicat_cipher.h declare:
+# every symbol include/replicat_chunker.h, replicat_digest.h, replicat_cipher.h and
+# replicat_restore.h declare:
 # name -> (restype, argtypes)
 _u64, _i64, _u32, _int, _p = ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p
 SIGNATURES = {
@@ -128,6 +132,14 @@ SIGNATURES = {
     'rc_chacha_timing_enable': (_int, [_p, _int]),
     'rc_chacha_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
     'rc_poly1305_host': (_int, [_u64, _p, _p, _p, _p]),
+    # replicat_restore.h
+    'rc_restore_create': (_int, [_p, _int, _p, _p, ctypes.POINTER(_p)]),
+    'rc_restore_destroy': (None, [_p]),
+    'rc_restore_overhead': (_u32, [_p]),
+    'rc_restore_verify_device': (_int, [_p, _u64, _p, _p, _p, _p, _p, _p]),
+    'rc_restore_verify_host': (_int, [_p, _u64, _p, _p, _p, _p, _p]),
+    'rc_restore_timing_enable': (_int, [_p, _int]),
+    'rc_restore_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
 }
 
 
@@ -139,6 +151,11 @@ class ChunkerError(RuntimeError):
     def __init__(self, code, message):
         super().__init__(f'{message} (rc={code})')
         self.code = code
+
+
+class ChunkCorrupted(ChunkerError):
+    """A chunk's digest is not the one the snapshot recorded (RC_ERR_CORRUPT): the reference's
+    ReplicatError('Chunk at ... is corrupted') (repository.py:1738-1739)."""
 
 
 class ChunkerFault(ChunkerError):
@@ -204,4 +221,6 @@ def check(code):
         raise ChunkerUnavailable(msg)
     if code == RC_ERR_DEVICE_FAULT:
         raise ChunkerFault(code, msg)
+    if code == RC_ERR_CORRUPT:
+        raise ChunkCorrupted(code, msg)
     raise ChunkerError(code, msg)

@@ -15,6 +15,8 @@
 
 struct rc_chacha : rc_cipher::CipherCore {};
 
+rc_cipher::CipherCore *rc_cipher::core_of(rc_chacha *g) { return g; }
+
 namespace {
 
 using namespace rc_cipher;

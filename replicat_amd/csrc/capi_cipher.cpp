@@ -81,6 +81,8 @@ struct rc_gcm : rc_cipher::CipherCore {
     rc::DevBuf d_consts;  // te0 | sq
 };
 
+rc_cipher::CipherCore *rc_cipher::core_of(rc_gcm *g) { return g; }
+
 namespace {
 
 rc_gcm *self(rc_cipher::CipherCore *g) { return static_cast<rc_gcm *>(g); }

@@ -286,6 +286,11 @@ void rc_blake2b_destroy(rc_hasher *h) {
 
 uint32_t rc_blake2b_digest_size(const rc_hasher *h) { return h ? h->digest_size : 0; }
 uint32_t rc_hash_algorithm(const rc_hasher *h) { return h ? h->algo : 0; }
+}
+
+int rc_hasher_device(const rc_hasher *h) { return h->device; }
+
+extern "C" {
 
 int rc_blake2b_device(rc_hasher *h, uint64_t n, const uint8_t *const *d_ptrs, const uint64_t *lens,
                       uint8_t *d_out, void *hip_stream) {

@@ -152,3 +152,6 @@ int rc_hasher_enqueue_chunks(rc_hasher *h, uint64_t n, const uint8_t *const *d_p
                              const uint64_t *cut_base, const uint64_t *d_cuts,
                              const int64_t *d_counts, uint64_t total_cap, uint64_t bytes,
                              uint64_t longest, uint8_t *d_out, hipStream_t st);
+
+// The HIP device a hasher is bound to (capi_restore.cpp: hasher and cipher must share one).
+int rc_hasher_device(const rc_hasher *h);

@@ -117,4 +117,8 @@ int run_host(CipherCore *g, int mode, uint64_t n, const uint8_t *const *in, cons
 // "item i: N bytes exceed ..." where the cipher has a longest message
 int check_len(const CipherDesc &c, uint64_t i, uint64_t len);
 
+// The core of a handle of either family (capi_restore.cpp holds its cipher as a CipherCore).
+CipherCore *core_of(rc_gcm *g);
+CipherCore *core_of(rc_chacha *g);
+
 }  // namespace rc_cipher

@@ -188,6 +188,26 @@ class ChunkEncryption:
         return c.GpuAesGcm(key_bits=self.key_bits, nonce_bits=self.nonce_bits, device=device)
 
 
+def hashing_arguments(hashing, digest_size, hash_bits):
+    """(digest_size, hash_bits, the adapter's own keyword arguments) of a repository's hashing
+    adapter (adapters.from_config): 'blake2b' with digest_size (its `length`, default 64), or
+    'sha2' / 'sha3' with hash_bits (their `bits`, default 512), from which digest_size follows.
+    The producer and the restorer (replicat_amd/restore.py) take the same three arguments."""
+    if hashing == 'blake2b':
+        if hash_bits is not None:
+            raise ValueError('hash_bits belongs to sha2 / sha3; blake2b takes digest_size')
+        digest_size = 64 if digest_size is None else digest_size
+        return digest_size, hash_bits, {'length': digest_size}
+    if hashing in ('sha2', 'sha3'):
+        hash_bits = 512 if hash_bits is None else hash_bits
+        if hash_bits not in SHA_BITS:
+            raise ValueError('Invalid digest size')
+        if digest_size is not None and digest_size != hash_bits // 8:
+            raise ValueError(f'digest_size {digest_size} disagrees with hash_bits {hash_bits}')
+        return hash_bits // 8, hash_bits, {'bits': hash_bits}
+    raise ValueError(f'hashing must be blake2b, sha2 or sha3, not {hashing!r}')
+
+
 @dataclass
 class SnapshotStream:
     files: List[FileRecord]
@@ -378,24 +398,7 @@ class DeviceSnapshotProducer:
                  slots: int = 3, queues: str = 'own', read_threads: int = 4,
                  timeline: bool = False, hashing: str = 'blake2b',
                  hash_bits: Optional[int] = None):
-        # hashing / hash_bits: the repository's hashing adapter (adapters.from_config): 'blake2b'
-        # with digest_size (its `length`, default 64), or 'sha2' / 'sha3' with hash_bits (their
-        # `bits`, default 512), from which digest_size follows
-        if hashing == 'blake2b':
-            if hash_bits is not None:
-                raise ValueError('hash_bits belongs to sha2 / sha3; blake2b takes digest_size')
-            digest_size = 64 if digest_size is None else digest_size
-            self._hash_args = {'length': digest_size}
-        elif hashing in ('sha2', 'sha3'):
-            hash_bits = 512 if hash_bits is None else hash_bits
-            if hash_bits not in SHA_BITS:
-                raise ValueError('Invalid digest size')
-            if digest_size is not None and digest_size != hash_bits // 8:
-                raise ValueError(f'digest_size {digest_size} disagrees with hash_bits {hash_bits}')
-            digest_size = hash_bits // 8
-            self._hash_args = {'bits': hash_bits}
-        else:
-            raise ValueError(f'hashing must be blake2b, sha2 or sha3, not {hashing!r}')
+        digest_size, hash_bits, self._hash_args = hashing_arguments(hashing, digest_size, hash_bits)
         self.hashing, self.hash_bits = hashing, hash_bits
         import torch
         if device is None:
