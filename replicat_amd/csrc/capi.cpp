@@ -466,8 +466,8 @@ int abandon_launch(Workspace &ws, hipStream_t ts, hipStream_t xs, int rc) {
     return rc;
 }
 
-// batches of at least this many streams walk their chains one lane per stream (when the
-// windows are small and every stream is one segment: kernels.hip rc_lane_chain_kernel)
+// batches of at least this many streams walk their chains a quad of lanes per stream (when the
+// windows are small and every stream is one segment: kernels.hip rc_quad_chain_kernel)
 constexpr uint64_t kLaneMinStreams = 256;
 
 int upload_and_launch(rc_chunker *ch, Workspace &ws, const Plan &plan, ChainParams prm,
@@ -532,12 +532,11 @@ int upload_and_launch(rc_chunker *ch, Workspace &ws, const Plan &plan, ChainPara
     GroupRecord *grp = ch->groups ? group_records(ws, plan) : nullptr;
     prm.grp = grp;
     prm.n_tiles = plan.n_tiles;
-    // lane-per-stream chain (kernels.hip rc_lane_chain_kernel) for batches of many streams;
-    // RC_LANE_CHAIN: auto, 0 never, 1 whatever the count, lane one lane per stream (not a quad)
+    // quad-per-stream chain (kernels.hip rc_quad_chain_kernel) for batches of many streams;
+    // RC_LANE_CHAIN: auto, 0 never, 1 whatever the count
     switch (ch->knobs[knLaneChain]) {
     case 1: prm.lane = 0u; break;
     case 2: prm.lane = 2u; break;
-    case 3: prm.lane = 3u; break;
     default: prm.lane = plan.n >= kLaneMinStreams ? 1u : 0u;
     }
     // 32-bit chain steps: small windows (the one-row record cache) and key indices < 2^32

@@ -106,7 +106,7 @@ struct ChainParams {
     uint64_t n_tiles;     // tiles of the call (records and group bounds hold n_tiles + 1)
     uint32_t open;        // RC_OPEN: non-final prefix, no tail rule
     uint32_t lean;        // small windows and every stream < 16 GiB: 32-bit chain steps
-    uint32_t lane;        // lane-per-stream chain allowed (rc_lane_chain_kernel; 2 = forced)
+    uint32_t lane;        // quad-per-stream chain allowed (rc_quad_chain_kernel; 2 = forced)
     uint32_t hot;         // the group records' hot threshold (group_hot_threshold)
     // the call's fault stamp (the workspace counter buffer's kCtrStampWord, written by the
     // edge kernel) and this call's epoch: equal = the tile kernel took its fail-safe stop, the

@@ -185,8 +185,9 @@ __device__ __forceinline__ void stage_chain_tables(const KeyTables *tab) {
 }
 
 // (key desc, index asc) improvement test: the lexicographic order makes the merge of ranges
-// and records independent of the order in which a lane visits them.
-__device__ __forceinline__ void take_best(uint64_t k, uint64_t j, uint64_t &bk, uint64_t &bj) {
+// and records independent of the order in which a lane visits them.  I: the index type.
+template <typename I>
+__device__ __forceinline__ void take_best(uint64_t k, I j, uint64_t &bk, I &bj) {
     if (k > bk || (k == bk && j < bj)) {
         bk = k;
         bj = j;
@@ -757,7 +758,7 @@ struct UnitGrab {
 // G > 1: also grp[t] = the tile's group bounds (GroupRecord: the top-16 maximum of each of its
 // G key groups, keys that do not exist counting as 0, and the maximum outside the lane holding
 // it), upper bounds the chains use to leave most of an edge range unscanned (chain_step,
-// rc_lane_chain_kernel).
+// rc_quad_chain_kernel).
 //
 // Tiles the fast path cannot settle -- a candidate lane holding its top-16 maximum twice --
 // are listed per unit for the edge kernel: xlist[b + i] (i < xcount[u], b the unit's first
@@ -1260,24 +1261,61 @@ struct EdgeRange {
 
 enum : int { kStepStop = 0, kStepCut = 1, kStepTail1 = 2, kStepTail2 = 3 };
 
+// ---- the cut rule: the reference's next_cut decision, the one copy every walker takes it from
+// (chain_step, chain_step_small, rc_quad_chain_kernel).
+//
+// The argmax cut's offset from the chunk start: 4 bytes per key from key s4 (the chunk start's)
+// to the window's best key bj (bk its value; 0: no key taken), rounded up to min_length.
+// I: the walker's index type.
+template <typename I>
+__device__ __forceinline__ I argmax_offset(uint64_t bk, I bj, I s4, I minl) {
+    I idx = bk > 0 ? 4 * (bj - s4) : 0;
+    if (idx < minl) idx = (minl + 3) & ~(I)3;  // adapters.cpp:66-67
+    return idx;
+}
+
+// The step's cut(s) from chunk start `pos` (rem = L - pos bytes left), once the window is
+// settled.  argmax: the step looked for an argmax cut, and idx is its offset (argmax_offset);
+// far: rem >= 2 max_length, as the walker has computed it already, at its own index width.
+__device__ __forceinline__ int step_cuts(bool argmax, uint64_t idx, bool far, bool open,
+                                         uint64_t pos, uint64_t rem, uint64_t minl, uint64_t maxl,
+                                         uint64_t L, uint64_t &c1, uint64_t &c2) {
+    if (open && !argmax) return kStepStop;  // a non-final next_cut returns 0: wait
+    if (argmax) {
+        if (idx != 0) {
+            c1 = pos + idx;
+            return kStepCut;
+        }
+        if (far || open) return kStepStop;  // min_length == 0 (S7 UB)
+    }
+    uint64_t c;  // the tail rule (adapters.cpp:48-55)
+    if (rem <= maxl) c = rem;
+    else if (rem < maxl + minl) c = rem / 2;
+    else c = maxl;
+    if (c == 0) return kStepStop;
+    c1 = pos + c;
+    if (c < rem) {
+        c2 = L;
+        return kStepTail2;
+    }
+    return kStepTail1;
+}
+
 // Trim the key range [a, b] inside tile `te` to the groups whose top-16 maximum (gm: u16 per
-// group) reaches tb16; an empty result becomes a > b.  Returns whether the range changed.
-__device__ __forceinline__ bool trim_groups(uint64_t gm, uint64_t te, uint32_t tb16, uint64_t &a,
-                                            uint64_t &b) {
-    const uint64_t tj0 = te * kTileKeys;
+// group) reaches tb16; an empty result becomes a > b.  I: the walker's index type.
+template <typename I>
+__device__ __forceinline__ void trim_groups(uint64_t gm, I te, uint32_t tb16, I &a, I &b) {
+    const I tj0 = te * kTileKeys;
     uint32_t ga = (uint32_t)((a - tj0) / kGroupKeys), gb = (uint32_t)((b - tj0) / kGroupKeys);
-    const uint32_t ga0 = ga, gb0 = gb;
     while (ga <= gb && ((gm >> (16 * ga)) & 0xffffu) < tb16) ++ga;
     while (gb > ga && ((gm >> (16 * gb)) & 0xffffu) < tb16) --gb;
     if (ga > gb) {
         a = 1;
         b = 0;
-        return true;
+        return;
     }
-    if (ga == ga0 && gb == gb0) return false;
-    a = max(a, tj0 + (uint64_t)ga * kGroupKeys);
-    b = min(b, tj0 + (uint64_t)(gb + 1) * kGroupKeys - 1);
-    return true;
+    a = max(a, tj0 + (I)ga * kGroupKeys);
+    b = min(b, tj0 + (I)(gb + 1) * kGroupKeys - 1);
 }
 
 // A walker's window onto its stream's tile records, held in registers across chain steps:
@@ -1333,8 +1371,79 @@ struct RecCache {
 };
 
 
+// An edge range [a, b] inside one tile needs no scan when that tile's record (rk, rj) -- its
+// FIRST maximal key -- lies in the range (the first maximum of a set is the first maximum of
+// every subset holding it; the record is then folded into the best), or when the tile's keys
+// are all 0 (never taken, adapters.cpp:60-63).  Otherwise the record still bounds the range
+// from above: the head range (indices below every full tile's) cannot win when its bound is
+// below the records' best, the tail range (kTail: indices above) not even when it equals it
+// (index asc breaks the tie) -- and the final best is at least the records' best.  Returns
+// whether the range is settled.  I: the walker's index type.
+template <bool kTail, typename I>
+__device__ __forceinline__ bool edge_settled(uint64_t rk, I rj, I a, I b, uint64_t &bk, I &bj) {
+    const bool inr = rk != 0 && rj >= a && rj <= b;
+    if (inr) take_best(rk, rj, bk, bj);
+    return rk == 0 || inr || (kTail ? rk <= bk : rk < bk);
+}
+
+// The wave steps' scan of the edge ranges their records left: [a0, b0] (head) and [a1, b1]
+// (tail), an empty one as a > b, of a window whose best so far is (bk, bj).  Both ranges at
+// top-16 precision (EdgeRange), then the exact keys of the candidates -- the lanes holding the
+// ranges' top-16 maximum, when that reaches the best's top 16 bits -- folded into (bk, bj).
+template <typename I>
+__device__ __forceinline__ void scan_edges(const uint64_t *tl, const uint64_t *th,
+                                           const uint32_t *pf, const ChainStream &st, I a0, I b0,
+                                           I a1, I b1, uint32_t lb_a, uint32_t lb_b, uint64_t &bk,
+                                           I &bj) {
+    if (a0 > b0 && a1 > b1) return;
+    EdgeRange r0, r1;
+    r0.init(st.base, st.L / 4 - 1, a0, b0, 0);
+    r1.init(st.base, st.L / 4 - 1, a1, b1, 1);
+    uint32_t w0[kEdgeIters][4], w1[kEdgeIters][4];
+    uint32_t acc_first = 0, acc_last = 0;
+    if (r0.more()) r0.load(w0);
+    if (r1.more()) r1.load(w1);
+    // a range's next batch is issued as soon as its registers are consumed, so the
+    // other range's compute covers its latency
+    for (;;) {
+        const bool m0 = r0.more(), m1 = r1.more();
+        if (!m0 && !m1) break;
+        if (m0) {
+            r0.template compute<true>(w0, lb_a, lb_b, pf, acc_first, acc_last);
+            if (r0.more()) r0.load(w0);
+        }
+        if (m1) {
+            r1.template compute<true>(w1, lb_a, lb_b, pf, acc_first, acc_last);
+            if (r1.more()) r1.load(w1);
+        }
+    }
+    const uint32_t m = wave_max_u32(acc_first);
+    if (!((m & 0x8000u) && (m >> 16) >= (uint32_t)(bk >> 48))) return;
+    const bool cand = (acc_first >> 16) == (m >> 16) && (acc_first & 0x8000u);
+    const uint32_t fl = 511u - (acc_first & 0x1ffu), ll = acc_last & 0x1ffu;
+    if (__any(cand && fl != ll)) {
+        // a candidate lane holds its top-16 maximum twice: exact scan of the edges
+        uint64_t ek = 0, ej = ~0ull;
+        scan_ranges<kChainScanUnroll>(tl, th, st.base, a0, b0, a1, b1, ek, ej);
+        uint64_t bj64 = bj == (I)~(I)0 ? ~0ull : bj;  // "no key yet" at either width
+        take_best(ek, ej, bk, bj64);
+        wave_best(bk, bj64);
+        bj = (I)bj64;
+    } else {
+        const uint32_t lo = fl & 255u;  // lane-local index within its range
+        const I jc = ((fl < 256 ? a0 : a1) & ~(I)3) + 256u * (lo >> 2) + 4u * lane_id() + (lo & 3);
+        const I jl = cand ? jc : a0 <= b0 ? a0 : a1;  // any valid index
+        const uint64_t k = full_key(tl, th, ld_u32(st.base + 4ull * jl - 4),
+                                    ld_u32(st.base + 4ull * jl));
+        for (uint64_t cm = __ballot(cand); cm; cm &= cm - 1) {
+            const int l = __builtin_ctzll(cm);
+            take_best(lane_u64(k, l), (I)lane_u64(jl, l), bk, bj);
+        }
+    }
+}
+
 // One chain step from chunk start `pos` (< L): an argmax cut (adapters.cpp:59-69), or the tail
-// rule's one or two final cuts (adapters.cpp:48-55), or stop (non-final wait / S7 UB).
+// rule's one or two final cuts, or stop (non-final wait / S7 UB): step_cuts.
 // prm.max_steps == 0 is the raw single next_cut: c1 = the argmax offset, whatever its value.
 template <int R>
 __device__ int chain_step(const uint64_t *tl, const uint64_t *th, const uint32_t *pf,
@@ -1344,8 +1453,8 @@ __device__ int chain_step(const uint64_t *tl, const uint64_t *th, const uint32_t
     const uint64_t minl = prm.min_length, maxl = prm.max_length, T = prm.window;
     const bool single = prm.max_steps == 0;
     const uint64_t rem = st.L - pos;
-    const bool argmax = single || (st.P >= pos && st.P - pos >= maxl) || rem >= 2 * maxl;
-    if (prm.open && !argmax) return kStepStop;  // a non-final next_cut returns 0: wait
+    const bool far = rem >= 2 * maxl;
+    const bool argmax = single || (st.P >= pos && st.P - pos >= maxl) || far;
     if (argmax) {
         // window keys j in [pos/4 + 1, pos/4 + T]  (i = 4 .. < max, adapters.cpp:59): the full
         // tiles inside it come from their records (exact keys); the two partial edge tiles are
@@ -1365,18 +1474,11 @@ __device__ int chain_step(const uint64_t *tl, const uint64_t *th, const uint32_t
                 a1 = t_hi * kTileKeys;
                 b1 = jb;
             }
-            // one round trip: the window's records and both edge tiles' records in flight
-            EdgeRange r0, r1;
-            r0.init(st.base, st.L / 4 - 1, a0, b0, 0);
-            r1.init(st.base, st.L / 4 - 1, a1, b1, 1);
-            uint32_t w0[kEdgeIters][4], w1[kEdgeIters][4];
-            uint32_t acc_first = 0, acc_last = 0;
-            // An edge range inside one tile needs no scan when that tile's record -- its FIRST
-            // maximal key -- lies in the range (the first maximum of a set is the first maximum
-            // of every subset holding it), or when the tile's keys are all 0 (never taken,
-            // adapters.cpp:60-63).
-            const bool one0 = r0.live && a0 / kTileKeys == b0 / kTileKeys;
-            const bool one1 = r1.live && a1 / kTileKeys == b1 / kTileKeys;
+            // one round trip: the window's records and both edge tiles' records in flight.
+            // An edge range inside one tile may be settled by that tile's record (edge_settled).
+            bool live0 = a0 <= b0, live1 = a1 <= b1;
+            const bool one0 = live0 && a0 / kTileKeys == b0 / kTileKeys;
+            const bool one1 = live1 && a1 / kTileKeys == b1 / kTileKeys;
             const uint64_t te0 = a0 / kTileKeys, te1 = a1 / kTileKeys;
             // the tiles this step reads records of: the window's full tiles and the edge tiles
             uint64_t need_lo = ~0ull, need_hi = 0;
@@ -1415,18 +1517,8 @@ __device__ int chain_step(const uint64_t *tl, const uint64_t *th, const uint32_t
             if (one0 && !g0) er0 = cache.get(te0, gm0);
             if (one1 && !g1) er1 = cache.get(te1, gm1);
             wave_best(bk, bj);
-            // Otherwise the record still bounds the range from above: the head range (indices
-            // below every full tile's) cannot win when its bound is below the records' best,
-            // the tail range (indices above) not even when it equals it (index asc breaks the
-            // tie) -- and the final best is at least the records' best.
-            if (one0 && (er0.key == 0 || (er0.j >= a0 && er0.j <= b0) || er0.key < bk)) {
-                if (er0.key != 0 && er0.j >= a0 && er0.j <= b0) take_best(er0.key, er0.j, bk, bj);
-                r0.live = false;
-            }
-            if (one1 && (er1.key == 0 || (er1.j >= a1 && er1.j <= b1) || er1.key <= bk)) {
-                if (er1.key != 0 && er1.j >= a1 && er1.j <= b1) take_best(er1.key, er1.j, bk, bj);
-                r1.live = false;
-            }
+            if (one0 && edge_settled<false>(er0.key, er0.j, a0, b0, bk, bj)) live0 = false;
+            if (one1 && edge_settled<true>(er1.key, er1.j, a1, b1, bk, bj)) live1 = false;
             // With group maxima (small windows): a key group whose top-16 maximum is below bk's
             // top 16 bits holds no key >= bk, so it cannot win, head or tail; the range left to
             // scan is trimmed to its groups from the first to the last one that can.  The head
@@ -1434,79 +1526,28 @@ __device__ int chain_step(const uint64_t *tl, const uint64_t *th, const uint32_t
             // so its record rarely settles the head; its groups after that key usually do.
             if (prm.grp) {
                 const uint32_t tb16 = (uint32_t)(bk >> 48);
-                if (one0 && r0.live && trim_groups(gm0, te0, tb16, a0, b0))
-                    r0.init(st.base, st.L / 4 - 1, a0, b0, 0);
-                if (one1 && r1.live && trim_groups(gm1, te1, tb16, a1, b1))
-                    r1.init(st.base, st.L / 4 - 1, a1, b1, 1);
+                if (one0 && live0) trim_groups(gm0, te0, tb16, a0, b0);
+                if (one1 && live1) trim_groups(gm1, te1, tb16, a1, b1);
             }
             // the few ranges left are scanned: their first batches only now (a second round
             // trip for them; none at all for the rest)
-            if (r0.more()) r0.load(w0);
-            if (r1.more()) r1.load(w1);
+            if (!live0) a0 = 1, b0 = 0;
+            if (!live1) a1 = 1, b1 = 0;
             RC_STAMP(2);
-            // a range's next batch is issued as soon as its registers are consumed, so the
-            // other range's compute covers its latency
-            for (;;) {
-                const bool m0 = r0.more(), m1 = r1.more();
-                if (!m0 && !m1) break;
-                if (m0) {
-                    r0.template compute<true>(w0, lb_a, lb_b, pf, acc_first, acc_last);
-                    if (r0.more()) r0.load(w0);
-                }
-                if (m1) {
-                    r1.template compute<true>(w1, lb_a, lb_b, pf, acc_first, acc_last);
-                    if (r1.more()) r1.load(w1);
-                }
-            }
+            scan_edges<uint64_t>(tl, th, pf, st, a0, b0, a1, b1, lb_a, lb_b, bk, bj);
             RC_STAMP(3);
-            const uint32_t m = wave_max_u32(acc_first);
-            if ((m & 0x8000u) && (m >> 16) >= (uint32_t)(bk >> 48)) {
-                const bool cand = (acc_first >> 16) == (m >> 16) && (acc_first & 0x8000u);
-                const uint32_t fl = 511u - (acc_first & 0x1ffu), ll = acc_last & 0x1ffu;
-                if (__any(cand && fl != ll)) {
-                    // a candidate lane holds its top-16 maximum twice: exact scan of the edges
-                    uint64_t ek = 0, ej = ~0ull;
-                    scan_ranges<kChainScanUnroll>(tl, th, st.base, a0, b0, a1, b1, ek, ej);
-                    take_best(ek, ej, bk, bj);
-                    wave_best(bk, bj);
-                } else {
-                    const uint32_t lo = fl & 255u;  // lane-local index within its range
-                    const uint64_t jc = ((fl < 256 ? a0 : a1) & ~3ull) + 256ull * (lo >> 2) +
-                                        4ull * lane_id() + (lo & 3);
-                    const uint64_t jl = cand ? jc : (uint64_t)a0;  // any valid index
-                    const uint64_t k = full_key(tl, th, ld_u32(st.base + 4 * jl - 4),
-                                                ld_u32(st.base + 4 * jl));
-                    for (uint64_t cm = __ballot(cand); cm; cm &= cm - 1) {
-                        const int l = __builtin_ctzll(cm);
-                        take_best(lane_u64(k, l), lane_u64(jl, l), bk, bj);
-                    }
-                }
-            }
         }
         RC_STAMP(4);
-        uint64_t idx = bk > 0 ? 4 * (bj - s4) : 0;
-        if (idx < minl) idx = (minl + 3) & ~3ull;  // adapters.cpp:66-67
+        const uint64_t idx = argmax_offset<uint64_t>(bk, bj, s4, minl);
         if (single) {
             c1 = idx;
             return kStepCut;
         }
-        if (idx != 0) {
-            c1 = pos + idx;
-            return kStepCut;
-        }
-        if (rem >= 2 * maxl || prm.open) return kStepStop;  // min_length == 0 (S7 UB)
+        return step_cuts(true, idx, far, prm.open, pos, rem, minl, maxl, st.L, c1, c2);
     }
-    uint64_t c;
-    if (rem <= maxl) c = rem;
-    else if (rem < maxl + minl) c = rem / 2;
-    else c = maxl;
-    if (c == 0) return kStepStop;
-    c1 = pos + c;
-    if (c < rem) {
-        c2 = st.L;
-        return kStepTail2;
-    }
-    return kStepTail1;
+    // no argmax cut to look for (two calls, each with a constant `argmax`: one call fed by a
+    // variable kept more values live across the window and spilled more SGPRs)
+    return step_cuts(false, 0, far, prm.open, pos, rem, minl, maxl, st.L, c1, c2);
 }
 
 // ---- the chain step for small windows (prm.lean): the same decisions as chain_step, with the
@@ -1521,26 +1562,7 @@ __device__ __forceinline__ bool ge64(uint64_t a, uint32_t b) {  // a >= b with S
 }
 
 __device__ __forceinline__ void take_best32(uint64_t k, uint32_t j, uint64_t &bk, uint32_t &bj) {
-    if (k > bk || (k == bk && j < bj)) {
-        bk = k;
-        bj = j;
-    }
-}
-
-// trim_groups on 32-bit indices: the range [a, b] inside tile te, emptied as a > b
-__device__ __forceinline__ void trim_groups32(uint64_t gm, uint32_t te, uint32_t tb16,
-                                              uint32_t &a, uint32_t &b) {
-    const uint32_t tj0 = te * kTileKeys;
-    uint32_t ga = (a - tj0) / kGroupKeys, gb = (b - tj0) / kGroupKeys;
-    while (ga <= gb && ((gm >> (16 * ga)) & 0xffffu) < tb16) ++ga;
-    while (gb > ga && ((gm >> (16 * gb)) & 0xffffu) < tb16) --gb;
-    if (ga > gb) {
-        a = 1;
-        b = 0;
-        return;
-    }
-    a = max(a, tj0 + ga * kGroupKeys);
-    b = min(b, tj0 + (gb + 1) * kGroupKeys - 1);
+    take_best(k, j, bk, bj);
 }
 
 __device__ int chain_step_small(const uint64_t *tl, const uint64_t *th, const uint32_t *pf,
@@ -1551,8 +1573,8 @@ __device__ int chain_step_small(const uint64_t *tl, const uint64_t *th, const ui
     const uint32_t T = (uint32_t)prm.window;
     const bool single = prm.max_steps == 0;
     const uint64_t rem = st.L - pos;
-    const bool argmax = single || (st.P >= pos && ge64(st.P - pos, maxl)) || ge64(rem, 2 * maxl);
-    if (prm.open && !argmax) return kStepStop;
+    const bool far = ge64(rem, 2 * maxl);
+    const bool argmax = single || (st.P >= pos && ge64(st.P - pos, maxl)) || far;
     if (argmax) {
         const uint32_t s4 = (uint32_t)(pos >> 2), jmax = (uint32_t)st.jmax;
         const uint32_t ja = s4 + 1, jb = min(s4 + T, jmax);
@@ -1617,107 +1639,28 @@ __device__ int chain_step_small(const uint64_t *tl, const uint64_t *th, const ui
                 ej1 = (uint32_t)__builtin_amdgcn_readlane((uint32_t)cache.v[0].j, l);
                 if (prm.grp) gm1 = lane_u64(cache.g[0], l);
             }
-            // settle the edge ranges by their tiles' records, then trim them by the group
-            // maxima (chain_step explains both rules)
+            // settle the edge ranges by their tiles' records (edge_settled), then trim them by
+            // the group maxima (chain_step explains the rule)
             bool live0 = a0 <= b0, live1 = a1 <= b1;
-            if (one0 && (ek0 == 0 || (ej0 >= a0 && ej0 <= b0) || ek0 < bk)) {
-                if (ek0 != 0 && ej0 >= a0 && ej0 <= b0) take_best32(ek0, ej0, bk, bj);
-                live0 = false;
-            }
-            if (one1 && (ek1 == 0 || (ej1 >= a1 && ej1 <= b1) || ek1 <= bk)) {
-                if (ek1 != 0 && ej1 >= a1 && ej1 <= b1) take_best32(ek1, ej1, bk, bj);
-                live1 = false;
-            }
+            if (one0 && edge_settled<false>(ek0, ej0, a0, b0, bk, bj)) live0 = false;
+            if (one1 && edge_settled<true>(ek1, ej1, a1, b1, bk, bj)) live1 = false;
             if (prm.grp) {
                 const uint32_t tb16 = (uint32_t)(bk >> 48);
-                if (one0 && live0) {
-                    trim_groups32(gm0, te0, tb16, a0, b0);
-                    live0 = a0 <= b0;
-                }
-                if (one1 && live1) {
-                    trim_groups32(gm1, te1, tb16, a1, b1);
-                    live1 = a1 <= b1;
-                }
+                if (one0 && live0) trim_groups(gm0, te0, tb16, a0, b0);
+                if (one1 && live1) trim_groups(gm1, te1, tb16, a1, b1);
             }
-            if (live0 || live1) {
-                if (!live0) {
-                    a0 = 1;
-                    b0 = 0;
-                }
-                if (!live1) {
-                    a1 = 1;
-                    b1 = 0;
-                }
-                EdgeRange r0, r1;
-                r0.init(st.base, st.L / 4 - 1, a0, b0, 0);
-                r1.init(st.base, st.L / 4 - 1, a1, b1, 1);
-                uint32_t w0[kEdgeIters][4], w1[kEdgeIters][4];
-                uint32_t acc_first = 0, acc_last = 0;
-                if (r0.more()) r0.load(w0);
-                if (r1.more()) r1.load(w1);
-                for (;;) {
-                    const bool m0 = r0.more(), m1 = r1.more();
-                    if (!m0 && !m1) break;
-                    if (m0) {
-                        r0.template compute<true>(w0, lb_a, lb_b, pf, acc_first, acc_last);
-                        if (r0.more()) r0.load(w0);
-                    }
-                    if (m1) {
-                        r1.template compute<true>(w1, lb_a, lb_b, pf, acc_first, acc_last);
-                        if (r1.more()) r1.load(w1);
-                    }
-                }
-                const uint32_t m = wave_max_u32(acc_first);
-                if ((m & 0x8000u) && (m >> 16) >= (uint32_t)(bk >> 48)) {
-                    const bool cand = (acc_first >> 16) == (m >> 16) && (acc_first & 0x8000u);
-                    const uint32_t fl = 511u - (acc_first & 0x1ffu), ll = acc_last & 0x1ffu;
-                    if (__any(cand && fl != ll)) {
-                        // a candidate lane holds its top-16 maximum twice: exact scan
-                        uint64_t ek = 0, ej = ~0ull;
-                        scan_ranges<kChainScanUnroll>(tl, th, st.base, a0, b0, a1, b1, ek, ej);
-                        uint64_t bj64 = bj == ~0u ? ~0ull : bj;
-                        take_best(ek, ej, bk, bj64);
-                        wave_best(bk, bj64);
-                        bj = (uint32_t)bj64;
-                    } else {
-                        const uint32_t lo = fl & 255u;  // lane-local index within its range
-                        const uint32_t jc = ((fl < 256 ? a0 : a1) & ~3u) + 256u * (lo >> 2) +
-                                            4u * lane + (lo & 3);
-                        const uint32_t jl = cand ? jc : a0 <= b0 ? a0 : a1;  // any valid index
-                        const uint64_t k = full_key(tl, th, ld_u32(st.base + 4ull * jl - 4),
-                                                    ld_u32(st.base + 4ull * jl));
-                        for (uint64_t cm = __ballot(cand); cm; cm &= cm - 1) {
-                            const int l = __builtin_ctzll(cm);
-                            take_best32(lane_u64(k, l),
-                                        (uint32_t)__builtin_amdgcn_readlane(jl, l), bk, bj);
-                        }
-                    }
-                }
-            }
+            if (!live0) a0 = 1, b0 = 0;
+            if (!live1) a1 = 1, b1 = 0;
+            scan_edges<uint32_t>(tl, th, pf, st, a0, b0, a1, b1, lb_a, lb_b, bk, bj);
         }
-        uint32_t idx = bk > 0 ? 4u * (bj - s4) : 0u;
-        if (idx < minl) idx = (minl + 3) & ~3u;  // adapters.cpp:66-67
+        const uint32_t idx = argmax_offset<uint32_t>(bk, bj, s4, minl);
         if (single) {
             c1 = idx;
             return kStepCut;
         }
-        if (idx != 0) {
-            c1 = pos + idx;
-            return kStepCut;
-        }
-        if (ge64(rem, 2 * maxl) || prm.open) return kStepStop;  // min_length == 0 (S7 UB)
+        return step_cuts(true, idx, far, prm.open, pos, rem, minl, maxl, st.L, c1, c2);
     }
-    uint64_t c;
-    if (rem <= maxl) c = rem;
-    else if (rem < (uint64_t)maxl + minl) c = rem / 2;
-    else c = maxl;
-    if (c == 0) return kStepStop;
-    c1 = pos + c;
-    if (c < rem) {
-        c2 = st.L;
-        return kStepTail2;
-    }
-    return kStepTail1;
+    return step_cuts(false, 0, far, prm.open, pos, rem, minl, maxl, st.L, c1, c2);
 }
 
 __device__ __forceinline__ uint64_t find_index(const uint64_t *base_arr, uint64_t n, uint64_t v) {
@@ -1820,35 +1763,34 @@ __global__ __launch_bounds__(kChainWaves * 64) void rc_spec_kernel(const KeyTabl
     }
 }
 
-// ---- the lane-per-stream chain (small windows, many single-segment streams)
+// ---- the per-stream chain (small windows, many single-segment streams)
 //
 // rc_spec_kernel walks one stream per WAVE: a step's decisions are scalar and its edge ranges
 // are scanned by the whole wave.  With 1 MiB streams and an 80 KB max_length (config 3 iii:
 // 65,536 streams x 22 steps) that is ~250 VALU + ~300 SALU per step and ~1.1 ms of a 13 ms
 // batch, almost all of it the scan of the head range -- the rest of the previous cut's group,
-// whose top-16 maximum is that cut's own key.  Here every LANE walks its own stream, and the
-// group bounds (GroupRecord) settle the edge ranges without a scan:
+// whose top-16 maximum is that cut's own key.  Here every stream is walked by a few lanes of its
+// own (a quad, below; at first one lane), every step's decisions are per lane, and the group
+// bounds (GroupRecord) settle the edge ranges without a scan:
 //   * the window's full tiles come from their records (16-byte loads, all in flight together);
 //   * a partial edge range is settled by its tile's record when the record lies in it, or
 //     excluded when the record is below the best (head) or at most the best (tail) -- as in
 //     chain_step;
 //   * otherwise each group the range overlaps is excluded when its top-16 maximum is below
 //     the best so far; when only the maximum's own lane l0 can reach it (the other lanes'
-//     bound is below), the walking lane evaluates the keys of lane l0 in the range itself:
+//     bound is below), the walking lanes evaluate the keys of lane l0 in the range themselves:
 //     kTileIters / G iterations of 4 keys, one 16-byte load and the word before each;
 //   * a group in which two lanes reach the bound (the window's maximum shares the previous
 //     cut's group: ~2 % of steps) is scanned exactly by the whole wave, lane after lane.
 // A key whose top 16 bits are below the best's cannot be >= it, so every rule is exact.
-constexpr int kLaneFull = 8;  // widest window of the lane chain: window keys / kTileKeys <= 8
+constexpr int kLaneFull = 8;  // widest window of this chain: window keys / kTileKeys <= 8
 constexpr int kLaneIters = kTileIters / kTileGroups;  // tile-kernel iterations per group
 
 // Group classification of one edge range [a, b] inside tile te: mk[q] = the lanes of group q
-// whose keys the walking lane evaluates (its hot lanes, when the best so far reaches the hot
+// whose keys the walking lanes evaluate (its hot lanes, when the best so far reaches the hot
 // threshold, at most kLaneHotMax of them), sc = the groups left to an exact scan (below the
 // threshold, or more hot lanes); a group whose top-16 maximum is below the best needs neither.
 constexpr uint32_t kLaneHotMax = 4;
-constexpr int kLaneTasks = 2;  // (group, lane) tasks per round of the lane chain (even; 4: slower,
-                               // every slot's scan is paid whether a lane has a task or not)
 
 __device__ __forceinline__ void lane_groups(bool live, const GroupRecord &g, uint32_t te,
                                             uint32_t a, uint32_t b, uint32_t t16, uint32_t hot,
@@ -1874,103 +1816,6 @@ __device__ __forceinline__ uint32_t top16_of(uint32_t e_lo_word, uint32_t e_hi_w
     return ((e_lo_word & 0xffff0000u) ^ (e_hi_word << 16)) >> 16;
 }
 
-// One lane's keys in one group: keys jq + 256 i .. jq + 256 i + 3 (i < kLaneIters), jq =
-// the group's first key + 4 l -- one 16-byte block per iteration and the word before it.
-struct LaneQuarter {
-    uint32_t w[kLaneIters][5];  // the word before each block, then the block's 4 words
-};
-
-// Loads only the iterations holding a key of [a, b] (none when a > b).  A loaded block holds
-// a key <= b <= jmax, hence a stream byte: it cannot cross a page.
-__device__ __forceinline__ void lq_load(const uint8_t *base, uint32_t jq, uint32_t a, uint32_t b,
-                                        LaneQuarter &x) {
-#pragma unroll
-    for (int i = 0; i < kLaneIters; ++i) {
-        const uint32_t j4 = jq + 256 * i;
-        u32x4 v = u32x4{0u, 0u, 0u, 0u};
-        uint32_t p = 0;
-        if (j4 <= b && j4 + 3 >= a) {
-            v = *as_global_x4(base + 4ull * j4);
-            p = ld_u32(base + 4ull * j4 - (j4 ? 4 : 0));
-        }
-        x.w[i][0] = p;
-        x.w[i][1] = v.x;
-        x.w[i][2] = v.y;
-        x.w[i][3] = v.z;
-        x.w[i][4] = v.w;
-    }
-}
-
-// The candidate among the keys of x in [a, b]: the one with the largest top-16 value (from the
-// prefilter) that reaches t16 -- a key with a smaller top-16 value is smaller -- and whether
-// another key shares that value (then every key of the lane is evaluated exactly: rare).
-struct LaneCand {
-    bool have, tie;
-    uint32_t ct, cj;
-};
-
-__device__ __forceinline__ LaneCand lq_scan(const uint32_t *pf, const LaneQuarter &x, uint32_t jq,
-                                            uint32_t a, uint32_t b, uint32_t t16) {
-    bool have = false, tie = false;
-    uint32_t ct = 0, cj = 0;
-#pragma unroll
-    for (int i = 0; i < kLaneIters; ++i) {
-        const uint32_t j4 = jq + 256 * i;
-        if (!(j4 <= b && j4 + 3 >= a)) continue;
-        uint32_t e[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) e[k] = pfc_entry(pf, x.w[i][k]);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t j = j4 + k, t = top16_of(e[k], e[k + 1]);
-            if (j >= a && j <= b && t >= t16) {
-                if (!have || t > ct) {
-                    have = true;
-                    tie = false;
-                    ct = t;
-                    cj = j;
-                } else if (t == ct) {
-                    tie = true;
-                }
-            }
-        }
-    }
-    return LaneCand{have, tie, ct, cj};
-}
-
-// Every key of lane jq's blocks in [a, b] exactly, its words read again (rolled: rare, small code)
-__device__ __forceinline__ void lq_all(const uint64_t *tl, const uint64_t *th, const uint8_t *base,
-                                       uint32_t jq, uint32_t a, uint32_t b, uint64_t &bk,
-                                       uint32_t &bj) {
-#pragma unroll 1
-    for (uint32_t i = 0; i < 4 * kLaneIters; ++i) {
-        const uint32_t j = jq + 256 * (i >> 2) + (i & 3);
-        if (j >= a && j <= b)
-            take_best32(full_key(tl, th, ld_u32(base + 4ull * j - 4), ld_u32(base + 4ull * j)), j, bk, bj);
-    }
-}
-
-// Two lanes' candidates folded into (bk, bj): their words read again (cache hits, both in
-// flight together) -- cheaper than carrying each candidate's words through the scan.
-__device__ __forceinline__ void lq_fold(const uint64_t *tl, const uint64_t *th, const uint8_t *base,
-                                        const LaneCand &c0, uint32_t jq0, uint32_t a0, uint32_t b0,
-                                        const LaneCand &c1, uint32_t jq1, uint32_t a1, uint32_t b1,
-                                        uint64_t &bk, uint32_t &bj) {
-    uint32_t w00 = 0, w01 = 0, w10 = 0, w11 = 0;
-    if (c0.have) {
-        w00 = ld_u32(base + 4ull * c0.cj - 4);
-        w01 = ld_u32(base + 4ull * c0.cj);
-    }
-    if (c1.have) {
-        w10 = ld_u32(base + 4ull * c1.cj - 4);
-        w11 = ld_u32(base + 4ull * c1.cj);
-    }
-    if (c0.have) take_best32(full_key(tl, th, w00, w01), c0.cj, bk, bj);
-    if (c1.have) take_best32(full_key(tl, th, w10, w11), c1.cj, bk, bj);
-    if (c0.tie) lq_all(tl, th, base, jq0, a0, b0, bk, bj);
-    if (c1.tie) lq_all(tl, th, base, jq1, a1, b1, bk, bj);
-}
-
 // Best exact key over [a, b] of one stream by the whole wave, 64 * U keys per memory round trip.
 template <int U>
 __device__ __forceinline__ void scan_range(const uint64_t *tl, const uint64_t *th,
@@ -1993,229 +1838,15 @@ __device__ __forceinline__ void scan_range(const uint64_t *tl, const uint64_t *t
     }
 }
 
-template <int F>  // full tiles per window held in flight (window keys / kTileKeys <= F)
-__global__ __launch_bounds__(256) void rc_lane_chain_kernel(const KeyTables *__restrict__ tab,
-                                                            StreamDesc d, uint64_t n_streams,
-                                                            ChainParams prm,
-                                                            const TileRecord *__restrict__ rec,
-                                                            uint64_t *__restrict__ cuts,
-                                                            int64_t *__restrict__ counts) {
-    if (call_faulted(prm)) {
-        fault_counts(counts, n_streams);
-        return;
-    }
-    stage_chain_tables(tab);
-    const uint32_t *pf = s_chain_lds;
-    const uint64_t *full = reinterpret_cast<const uint64_t *>(s_chain_lds + 1024);
-    const uint64_t *tl = full, *th = full + 1024;
-    const uint32_t lane = lane_id();
-    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid - lane >= n_streams) return;  // the whole wave is past the last stream
-    const bool mine = gid < n_streams;
-    const uint64_t s = mine ? gid : n_streams - 1;  // surplus lanes shadow the last stream, silent
-    const GroupRecord *grp = prm.grp;
-    const uint8_t *base = d.ptr[s];
-    const uint64_t L = d.len[s], P = d.last[s];
-    const uint64_t tb0 = d.tile_base[s], nt = d.tile_base[s + 1] - tb0;
-    uint64_t *out = cuts + d.cut_base[s];
-    const uint64_t cap = d.cut_cap[s];
-    const uint32_t jmax = L >= 8 ? (uint32_t)((L - 4) / 4) : 0u;
-    const uint32_t minl = (uint32_t)prm.min_length, maxl = (uint32_t)prm.max_length;
-    const uint32_t T = (uint32_t)prm.window;
-    // a stream tile's global index; the spare record at n_tiles for anything else (a safe
-    // address for loads whose values are not used)
-    auto gtile = [&](bool use, uint32_t t) -> uint64_t { return use && t < nt ? tb0 + t : prm.n_tiles; };
-
-    uint64_t pos = 0, n = 0;
-    bool walking = mine && L > 0 && prm.max_steps > 0, overflow = false;
-    RC_DIAG_ONLY(const bool diag = gid < 64;)  // wave 0: per-phase stamps
-    for (;;) {
-        if (!__any(walking)) break;
-        RC_LSTAMP(1);
-        const uint64_t rem = L - pos;
-        const bool argmax = (P >= pos && P - pos >= maxl) || rem >= 2ull * maxl;
-        const uint32_t s4 = (uint32_t)(pos >> 2);
-        const uint32_t ja = s4 + 1, jb = min(s4 + T, jmax);
-        const bool win = walking && argmax && T > 0 && ja <= jb;
-        // full tiles [t_lo, t_hi); head [a0, b0] inside tile te0, tail [a1, b1] inside tile te1
-        const uint32_t t_lo = (ja + kTileKeys - 1) / kTileKeys, t_hi = (jb + 1) / kTileKeys;
-        const uint32_t nf = win && t_hi > t_lo ? t_hi - t_lo : 0u;
-        const uint32_t a0 = ja, b0 = min(jb, t_lo * kTileKeys - 1), te0 = ja / kTileKeys;
-        const uint32_t a1 = t_hi * kTileKeys, b1 = jb, te1 = t_hi;
-        bool live0 = win && ja < t_lo * kTileKeys;
-        bool live1 = win && t_hi >= t_lo && jb >= a1;
-
-        TileRecord fr[F];
-#pragma unroll
-        for (int i = 0; i < F; ++i) fr[i] = rec[gtile((uint32_t)i < nf, t_lo + i)];
-        const TileRecord r0 = rec[gtile(live0, te0)], r1 = rec[gtile(live1, te1)];
-        const GroupRecord g0 = grp[gtile(live0, te0)], g1 = grp[gtile(live1, te1)];
-        // with them, the words of the previous cut's lane in the rest of its group (key s4 is
-        // in tile te0 whenever the head range is not empty)
-        const bool spec = live0;
-        const uint32_t lc = (s4 & 255u) >> 2, qc = (s4 & (kTileKeys - 1)) / kGroupKeys;
-        const uint32_t jqc = (s4 & ~(uint32_t)(kGroupKeys - 1)) + 4 * lc;
-        LaneQuarter x[kLaneTasks];
-        lq_load(base, jqc, spec ? a0 : 1u, spec ? b0 : 0u, x[0]);
-
-        uint64_t bk = 0;
-        uint32_t bj = ~0u;
-#pragma unroll
-        for (int i = 0; i < F; ++i)
-            if ((uint32_t)i < nf && fr[i].key != 0) take_best32(fr[i].key, (uint32_t)fr[i].j, bk, bj);
-        if (live0) {
-            const uint32_t rj = (uint32_t)r0.j;
-            const bool inr = r0.key != 0 && rj >= a0 && rj <= b0;
-            if (inr) take_best32(r0.key, rj, bk, bj);
-            if (r0.key == 0 || inr || r0.key < bk) live0 = false;
-        }
-        if (live1) {
-            const uint32_t rj = (uint32_t)r1.j;
-            const bool inr = r1.key != 0 && rj >= a1 && rj <= b1;
-            if (inr) take_best32(r1.key, rj, bk, bj);
-            if (r1.key == 0 || inr || r1.key <= bk) live1 = false;
-        }
-        uint32_t sc0, sc1;
-        RC_LSTAMP(2);
-        // tasks: the (group, lane) pairs to evaluate, as lane masks per group of the head's tile
-        // (h) and the tail's (t), popped head first
-        uint64_t h[kTileGroups], t[kTileGroups];
-        lane_groups(live0, g0, te0, a0, b0, (uint32_t)(bk >> 48), prm.hot, h, sc0);
-        lane_groups(live1, g1, te1, a1, b1, (uint32_t)(bk >> 48), prm.hot, t, sc1);
-        static_assert(kTileGroups == 4, "the task queue below spells out four groups");
-        auto any_task = [&]() { return (h[0] | h[1] | h[2] | h[3] | t[0] | t[1] | t[2] | t[3]) != 0; };
-        // pops the next task as its lane's first key block jq and range [a, b] (a > b: none)
-        auto task = [&](uint32_t &jq, uint32_t &a, uint32_t &b) {
-            int r = -1;
-            uint32_t q = 0, l = 0;
-#define RC_POP(M, R, Q)                            \
-    if (r < 0 && M) {                              \
-        l = (uint32_t)__builtin_ctzll(M);          \
-        M &= M - 1;                                \
-        r = R;                                     \
-        q = Q;                                     \
-    }
-            RC_POP(h[0], 0, 0) RC_POP(h[1], 0, 1) RC_POP(h[2], 0, 2) RC_POP(h[3], 0, 3)
-            RC_POP(t[0], 1, 0) RC_POP(t[1], 1, 1) RC_POP(t[2], 1, 2) RC_POP(t[3], 1, 3)
-#undef RC_POP
-            a = 1, b = 0;
-            if (r < 0) return;
-            jq = (r ? te1 : te0) * kTileKeys + q * kGroupKeys + 4 * l;
-            a = r ? a1 : a0;
-            b = r ? b1 : b0;
-        };
-
-        // the lanes' keys, kLaneTasks tasks per round with their loads in flight together.
-        // The first is, as a rule, the previous cut's own group and lane (that cut's key is the
-        // maximum of the previous window): its words came with the records.
-        bool first = false;
-#define RC_FIRST(Q)                                              \
-    if (spec && qc == Q && (h[Q] >> lc & 1u)) {                  \
-        h[Q] &= ~(1ull << lc);                                   \
-        first = true;                                            \
-    }
-        RC_FIRST(0) RC_FIRST(1) RC_FIRST(2) RC_FIRST(3)
-#undef RC_FIRST
-        uint32_t jq[kLaneTasks], ra[kLaneTasks], rb[kLaneTasks];
-        jq[0] = jqc, ra[0] = first ? a0 : 1u, rb[0] = first ? b0 : 0u;
-        for (;;) {
-            if (!__any(first || any_task())) break;
-#pragma unroll
-            for (int k = 0; k < kLaneTasks; ++k) {
-                if (k == 0 && first) continue;  // x[0] holds the previous cut's lane already
-                task(jq[k], ra[k], rb[k]);
-                lq_load(base, jq[k], ra[k], rb[k], x[k]);
-            }
-            const uint32_t t16 = (uint32_t)(bk >> 48);
-            LaneCand c[kLaneTasks];
-#pragma unroll
-            for (int k = 0; k < kLaneTasks; ++k) c[k] = lq_scan(pf, x[k], jq[k], ra[k], rb[k], t16);
-#pragma unroll
-            for (int k = 0; k < kLaneTasks; k += 2)
-                lq_fold(tl, th, base, c[k], jq[k], ra[k], rb[k], c[k + 1], jq[k + 1], ra[k + 1],
-                        rb[k + 1], bk, bj);
-            first = false;
-            RC_LSTAMP(3);
-        }
-        RC_LSTAMP(4);
-
-        // groups with too many hot lanes, or a best below the threshold: exact scans by the whole
-        // wave, one lane's range at a time
-        // (from the first to the last such group of the range), a group per memory round trip
-#pragma unroll 1
-        for (int r = 0; r < 2; ++r) {
-            const uint32_t sv = r == 0 ? +sc0 : +sc1;  // values, not a select of addresses
-            const uint32_t te = r == 0 ? +te0 : +te1, ra = r == 0 ? +a0 : +a1, rb = r == 0 ? +b0 : +b1;
-            uint32_t sa = 1, sb = 0;
-            if (sv) {
-                const uint32_t qlo = (uint32_t)__builtin_ctz(sv), qhi = 31u - (uint32_t)__builtin_clz(sv);
-                sa = max(ra, te * kTileKeys + qlo * kGroupKeys);
-                sb = min(rb, te * kTileKeys + (qhi + 1) * kGroupKeys - 1);
-            }
-            for (uint64_t m = __ballot(sa <= sb); m; m &= m - 1) {
-                const int l = __builtin_ctzll(m);
-                const uint32_t la = (uint32_t)__builtin_amdgcn_readlane(sa, l);
-                const uint32_t lb = (uint32_t)__builtin_amdgcn_readlane(sb, l);
-                const uint8_t *lbase = reinterpret_cast<const uint8_t *>(lane_u64((uint64_t)base, l));
-                uint64_t ek = 0, ej = ~0ull;
-                scan_range<kGroupKeys / 64>(tl, th, lbase, la, lb, ek, ej);
-                wave_best(ek, ej);
-                if (lane == (uint32_t)l && ek != 0) take_best32(ek, (uint32_t)ej, bk, bj);
-                RC_LSTAMP(5);
-            }
-        }
-        RC_LSTAMP(6);
-
-        // the step's cut(s): chain_step_small's decisions (adapters.cpp:48-69)
-        if (walking) {
-            int kind = kStepStop;
-            uint64_t c1 = 0, c2 = 0;
-            if (argmax) {
-                uint32_t idx = bk > 0 ? 4u * (bj - s4) : 0u;
-                if (idx < minl) idx = (minl + 3) & ~3u;  // adapters.cpp:66-67
-                if (idx != 0) {
-                    c1 = pos + idx;
-                    kind = kStepCut;
-                }
-            }
-            if (kind != kStepCut && !prm.open && !(argmax && rem >= 2ull * maxl)) {
-                uint64_t c;  // the tail rule (adapters.cpp:48-55); argmax with idx 0 is S7 UB
-                if (rem <= maxl) c = rem;
-                else if (rem < (uint64_t)maxl + minl) c = rem / 2;
-                else c = maxl;
-                if (c != 0) {
-                    c1 = pos + c;
-                    kind = kStepTail1;
-                    if (c < rem) {
-                        c2 = L;
-                        kind = kStepTail2;
-                    }
-                }
-            }
-            if (kind != kStepStop) {
-                if (n < cap) out[n++] = c1;
-                else overflow = true;
-                if (kind == kStepTail2) {
-                    if (n < cap) out[n++] = c2;
-                    else overflow = true;
-                }
-            }
-            if (kind != kStepCut || overflow) walking = false;
-            pos = c1;
-            if (pos >= L || n >= prm.max_steps) walking = false;
-        }
-    }
-    if (mine) counts[s] = overflow ? -1 : (int64_t)n;
-}
-
-// ---- the quad-per-stream chain: the lane chain with four lanes per stream
+// ---- the quad-per-stream chain: four lanes per stream
 //
-// The lane chain runs one wave per SIMD on config 3 (iii) (65,536 lanes), so a step is ~14 us
+// One lane per stream (the first form of this chain, since removed: DESIGN.md has its
+// measurements) runs one wave per SIMD on config 3 (iii) (65,536 lanes), so a step is ~14 us
 // of mostly dependent instructions with nothing to overlap them.  Here a QUAD of lanes walks
-// each stream: the steps are the same, but lane q of the quad loads the window's full-tile
-// record q (and q + 4) and takes iteration q of every (group, lane) task -- one 16-byte block,
-// the word before it and 4 keys, not 4 of each -- and the quad reduces records and candidates
-// with two DPP quad_perm exchanges.  Four waves per SIMD hide each other's latency.
+// each stream: lane q of the quad loads the window's full-tile record q (and q + 4) and takes
+// iteration q of every (group, lane) task -- one 16-byte block, the word before it and 4 keys,
+// not 4 of each -- and the quad reduces records and candidates with two DPP quad_perm
+// exchanges.  Four waves per SIMD hide each other's latency.
 template <int kCtrl>
 __device__ __forceinline__ uint32_t qperm32(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, kCtrl, 0xf, 0xf, true);
@@ -2322,6 +1953,8 @@ __global__ __launch_bounds__(256) void rc_quad_chain_kernel(const KeyTables *__r
     const uint32_t jmax = L >= 8 ? (uint32_t)((L - 4) / 4) : 0u;
     const uint32_t minl = (uint32_t)prm.min_length, maxl = (uint32_t)prm.max_length;
     const uint32_t T = (uint32_t)prm.window;
+    // a stream tile's global index; the spare record at n_tiles for anything else (a safe
+    // address for loads whose values are not used)
     auto gtile = [&](bool use, uint32_t t) -> uint64_t { return use && t < nt ? tb0 + t : prm.n_tiles; };
 
     uint64_t pos = 0, n = 0;
@@ -2331,10 +1964,12 @@ __global__ __launch_bounds__(256) void rc_quad_chain_kernel(const KeyTables *__r
         if (!__any(walking)) break;
         RC_LSTAMP(1);
         const uint64_t rem = L - pos;
-        const bool argmax = (P >= pos && P - pos >= maxl) || rem >= 2ull * maxl;
+        const bool far = rem >= 2ull * maxl;
+        const bool argmax = (P >= pos && P - pos >= maxl) || far;
         const uint32_t s4 = (uint32_t)(pos >> 2);
         const uint32_t ja = s4 + 1, jb = min(s4 + T, jmax);
         const bool win = walking && argmax && T > 0 && ja <= jb;
+        // full tiles [t_lo, t_hi); head [a0, b0] inside tile te0, tail [a1, b1] inside tile te1
         const uint32_t t_lo = (ja + kTileKeys - 1) / kTileKeys, t_hi = (jb + 1) / kTileKeys;
         const uint32_t nf = win && t_hi > t_lo ? t_hi - t_lo : 0u;
         const uint32_t a0 = ja, b0 = min(jb, t_lo * kTileKeys - 1), te0 = ja / kTileKeys;
@@ -2350,7 +1985,8 @@ __global__ __launch_bounds__(256) void rc_quad_chain_kernel(const KeyTables *__r
         }
         const TileRecord r0 = rec[gtile(live0, te0)], r1 = rec[gtile(live1, te1)];
         const GroupRecord g0 = grp[gtile(live0, te0)], g1 = grp[gtile(live1, te1)];
-        // the previous cut's lane in its group: iteration q of it
+        // with them, the words of the previous cut's lane in the rest of its group (key s4 is
+        // in tile te0 whenever the head range is not empty): iteration q of it
         const bool spec = live0;
         const uint32_t lc = (s4 & 255u) >> 2, qc = (s4 & (kTileKeys - 1)) / kGroupKeys;
         const uint32_t jqc = (s4 & ~(uint32_t)(kGroupKeys - 1)) + 4 * lc;
@@ -2363,25 +1999,18 @@ __global__ __launch_bounds__(256) void rc_quad_chain_kernel(const KeyTables *__r
         for (int i = 0; i < F / 4; ++i)
             if (4 * (uint32_t)i + q < nf && fr[i].key != 0) take_best32(fr[i].key, (uint32_t)fr[i].j, bk, bj);
         quad_best32(bk, bj);
-        if (live0) {
-            const uint32_t rj = (uint32_t)r0.j;
-            const bool inr = r0.key != 0 && rj >= a0 && rj <= b0;
-            if (inr) take_best32(r0.key, rj, bk, bj);
-            if (r0.key == 0 || inr || r0.key < bk) live0 = false;
-        }
-        if (live1) {
-            const uint32_t rj = (uint32_t)r1.j;
-            const bool inr = r1.key != 0 && rj >= a1 && rj <= b1;
-            if (inr) take_best32(r1.key, rj, bk, bj);
-            if (r1.key == 0 || inr || r1.key <= bk) live1 = false;
-        }
+        if (live0 && edge_settled<false>(r0.key, (uint32_t)r0.j, a0, b0, bk, bj)) live0 = false;
+        if (live1 && edge_settled<true>(r1.key, (uint32_t)r1.j, a1, b1, bk, bj)) live1 = false;
         uint32_t sc0, sc1;
         RC_LSTAMP(2);
+        // tasks: the (group, lane) pairs to evaluate, as lane masks per group of the head's tile
+        // (h) and the tail's (t), popped head first
         uint64_t h[kTileGroups], t[kTileGroups];
         lane_groups(live0, g0, te0, a0, b0, (uint32_t)(bk >> 48), prm.hot, h, sc0);
         lane_groups(live1, g1, te1, a1, b1, (uint32_t)(bk >> 48), prm.hot, t, sc1);
         static_assert(kTileGroups == 4, "the task queue below spells out four groups");
         auto any_task = [&]() { return (h[0] | h[1] | h[2] | h[3] | t[0] | t[1] | t[2] | t[3]) != 0; };
+        // pops the next task as its lane's first key block jq and range [a, b] (a > b: none)
         auto task = [&](uint32_t &jq, uint32_t &a, uint32_t &b) {
             int r = -1;
             uint32_t g = 0, l = 0;
@@ -2401,6 +2030,9 @@ __global__ __launch_bounds__(256) void rc_quad_chain_kernel(const KeyTables *__r
             a = r ? a1 : a0;
             b = r ? b1 : b0;
         };
+        // the lanes' keys, kQuadTasks tasks per round with their loads in flight together.
+        // The first is, as a rule, the previous cut's own group and lane (that cut's key is the
+        // maximum of the previous window): its words came with the records.
         bool first = false;
 #define RC_FIRST(Q)                                              \
     if (spec && qc == Q && (h[Q] >> lc & 1u)) {                  \
@@ -2436,10 +2068,11 @@ __global__ __launch_bounds__(256) void rc_quad_chain_kernel(const KeyTables *__r
         RC_LSTAMP(4);
 
         // groups with too many hot lanes, or a best below the threshold: exact scans by the whole
-        // wave, one stream's range at a time (ballot over the quads' first lanes)
+        // wave, one stream's range at a time (ballot over the quads' first lanes), from the first
+        // to the last such group of the range, a group per memory round trip
 #pragma unroll 1
         for (int r = 0; r < 2; ++r) {
-            const uint32_t sv = r == 0 ? +sc0 : +sc1;
+            const uint32_t sv = r == 0 ? +sc0 : +sc1;  // values, not a select of addresses
             const uint32_t te = r == 0 ? +te0 : +te1, ra_ = r == 0 ? +a0 : +a1, rb_ = r == 0 ? +b0 : +b1;
             uint32_t sa = 1, sb = 0;
             if (sv) {
@@ -2463,30 +2096,9 @@ __global__ __launch_bounds__(256) void rc_quad_chain_kernel(const KeyTables *__r
 
         // the step's cut(s), the same in the four lanes; lane 0 of the quad stores them
         if (walking) {
-            int kind = kStepStop;
             uint64_t c1 = 0, c2 = 0;
-            if (argmax) {
-                uint32_t idx = bk > 0 ? 4u * (bj - s4) : 0u;
-                if (idx < minl) idx = (minl + 3) & ~3u;  // adapters.cpp:66-67
-                if (idx != 0) {
-                    c1 = pos + idx;
-                    kind = kStepCut;
-                }
-            }
-            if (kind != kStepCut && !prm.open && !(argmax && rem >= 2ull * maxl)) {
-                uint64_t c;  // the tail rule (adapters.cpp:48-55); argmax with idx 0 is S7 UB
-                if (rem <= maxl) c = rem;
-                else if (rem < (uint64_t)maxl + minl) c = rem / 2;
-                else c = maxl;
-                if (c != 0) {
-                    c1 = pos + c;
-                    kind = kStepTail1;
-                    if (c < rem) {
-                        c2 = L;
-                        kind = kStepTail2;
-                    }
-                }
-            }
+            const uint32_t idx = argmax_offset<uint32_t>(bk, bj, s4, minl);
+            const int kind = step_cuts(argmax, idx, far, prm.open, pos, rem, minl, maxl, L, c1, c2);
             if (kind != kStepStop) {
                 if (n < cap) {
                     if (q == 0) out[n] = c1;
@@ -3140,20 +2752,10 @@ int rc_launch_chain(const KeyTables *d_tables, StreamDesc desc, uint64_t n_strea
                     uint64_t *d_seg_counts, bool any_multi, uint32_t join, void *stream) {
     if (n_streams == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    // many single-segment streams with small windows and group bounds: one lane per stream
+    // many single-segment streams with small windows and group bounds: a quad of lanes per stream
     if (prm.lane && prm.lean && prm.grp && !any_multi && n_segs == n_streams &&
         prm.max_steps != 0 && prm.window / kTileKeys <= (uint64_t)kLaneFull) {
         const bool narrow = prm.window / kTileKeys <= 4;
-        if (prm.lane == 3) {  // RC_LANE_CHAIN=lane: one lane per stream (comparison)
-            const uint64_t grid = (n_streams + 255) / 256;
-            if (narrow)
-                hipLaunchKernelGGL(rc_lane_chain_kernel<4>, dim3((unsigned)grid), dim3(256), 0, st,
-                                   d_tables, desc, n_streams, prm, d_records, d_cuts, d_counts);
-            else
-                hipLaunchKernelGGL(rc_lane_chain_kernel<kLaneFull>, dim3((unsigned)grid), dim3(256),
-                                   0, st, d_tables, desc, n_streams, prm, d_records, d_cuts, d_counts);
-            return launch_status("rc_lane_chain_kernel");
-        }
         const uint64_t grid = (n_streams + 63) / 64;  // a quad of lanes per stream
         if (narrow)
             hipLaunchKernelGGL(rc_quad_chain_kernel<4>, dim3((unsigned)grid), dim3(256), 0, st,

@@ -60,9 +60,9 @@ inline constexpr KnobSpec kKnobTable[kKnobCount] = {
     {"RC_OVERLAP_CUS", 32, 1, 1024, nullptr,
      "CUs reserved for the chain kernels of pipelined calls (rc_chunker_overlap overrides; "
      "must be below the device's CU count)"},
-    {"RC_LANE_CHAIN", 0, 0, 3, "auto|0|1|lane",
+    {"RC_LANE_CHAIN", 0, 0, 2, "auto|0|1",
      "chain kernel of small-window batches: auto (quads for >= 256 streams), 0 wave per "
-     "stream, 1 quads whatever the count, lane one lane per stream"},
+     "stream, 1 quads whatever the count"},
     {"RC_TILE_GROUPS", 0, 0, 2, "auto|0|1",
      "per-quarter group records of the tile kernel: auto (small windows), 0 never, 1 always"},
     {"RC_CHAIN_LEAN", 0, 0, 1, "auto|0",

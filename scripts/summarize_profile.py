@@ -26,7 +26,7 @@ def short(name):
     for k in ('rc_tile_kernel', 'rc_edge_kernel', 'rc_chain_kernel', 'rc_spec_kernel',
               'rc_join_kernel', 'rc_fill_kernel', 'rc_read_probe_kernel', 'rc_merge_kernel',
               'rc_scan_kernel', 'rc_copy_kernel', 'rc_mark_kernel', 'rc_quad_chain_kernel',
-              'rc_lane_chain_kernel', 'rc_fill_streams_kernel'):
+              'rc_fill_streams_kernel'):
         if k in name:
             return k
     return name[:60]

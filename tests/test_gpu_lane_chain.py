@@ -1,9 +1,10 @@
-"""GPU parity of the per-stream chains for small windows and many single-segment streams
-(kernels.hip rc_quad_chain_kernel: a quad of lanes per stream; rc_lane_chain_kernel: one lane),
-each walking its stream's cut chain from the tile records and the group bounds.  Every cut list
-against the oracle (the reference's next_cut restated, oracle/gclmul_oracle.c), with the quad
-chain forced (RC_LANE_CHAIN=1), the lane chain (=lane) and, for comparison, neither (=0: the
-wave-per-stream spec kernel).  Runs on an MI355X only (-m gpu)."""
+"""GPU parity of the chains for small windows and many single-segment streams (kernels.hip
+rc_quad_chain_kernel: a quad of lanes per stream, walking its stream's cut chain from the tile
+records and the group bounds).  Every cut list against the oracle (the reference's next_cut
+restated, oracle/gclmul_oracle.c), with the quad chain forced (RC_LANE_CHAIN=1), with the
+wave-per-stream spec kernel and its 32-bit step instead (=0), and -- on fewer cases -- with that
+kernel on the generic 64-bit step (=0 with RC_CHAIN_LEAN=0: rc_spec_kernel<1, false>, otherwise
+reached only by streams of 16 GiB or more).  Runs on an MI355X only (-m gpu)."""
 import random
 
 import numpy as np
@@ -44,17 +45,13 @@ def _data(rnd, kind, n, k):
 
 
 # (min, max): the config 3 (iii) pair, tiny windows inside one or two tiles, a window of 7.99
-# tiles (the lane chain's widest: 8 full-tile records in flight), min = max, a min of one key step
+# tiles (the quad chain's widest: 8 full-tile records in flight), min = max, a min of one key step
 PARAMS = [(2000, 80000), (500, 16384), (80000, 80000), (4, 4096 * 3), (12000, 131072),
           (64, 4096), (8, 3000)]
 
 
-@pytest.mark.parametrize('lane', ['1', 'lane', '0'])
-@pytest.mark.parametrize('mn,mx', PARAMS)
-@pytest.mark.parametrize('kind', ['random', 'zeros', 'periodic', 'sparse', 'splitmix'])
-def test_lane_chain_vs_oracle(monkeypatch, lane, mn, mx, kind):
-    o = _oracle()
-    monkeypatch.setenv('RC_LANE_CHAIN', lane)
+def _check_vs_oracle(mn, mx, kind):
+    """160 streams of at most 1 MiB under the knobs the caller has set: final and open."""
     rnd = random.Random(f'{mn}-{mx}-{kind}')
     key = b'\xff' * 16 if kind != 'splitmix' else synth.seeded_key(5)
     ch = GpuChunker(mn, mx, key)
@@ -75,6 +72,26 @@ def test_lane_chain_vs_oracle(monkeypatch, lane, mn, mx, kind):
     fulls = expected_cuts(datas, mn, mx, key, sizes)
     for d, g, full in zip(datas, got_open, fulls):
         assert g == open_prefix(full, len(d), mx), (mn, mx, kind, len(d))
+
+
+@pytest.mark.parametrize('lane', ['1', '0'])
+@pytest.mark.parametrize('mn,mx', PARAMS)
+@pytest.mark.parametrize('kind', ['random', 'zeros', 'periodic', 'sparse', 'splitmix'])
+def test_lane_chain_vs_oracle(monkeypatch, lane, mn, mx, kind):
+    _oracle()
+    monkeypatch.setenv('RC_LANE_CHAIN', lane)
+    _check_vs_oracle(mn, mx, kind)
+
+
+@pytest.mark.parametrize('mn,mx', [(2000, 80000), (64, 4096)])
+@pytest.mark.parametrize('kind', ['random', 'periodic'])
+def test_generic_step_small_window_vs_oracle(monkeypatch, mn, mx, kind):
+    """The small-window launch on the generic chain step (chain_step<1>), which no other test
+    reaches: the same batches and oracle comparison as above."""
+    _oracle()
+    monkeypatch.setenv('RC_LANE_CHAIN', '0')
+    monkeypatch.setenv('RC_CHAIN_LEAN', '0')
+    _check_vs_oracle(mn, mx, kind)
 
 
 def test_lane_chain_many_streams_default_switch(monkeypatch):

@@ -45,7 +45,7 @@ def _create():
 
 @pytest.mark.parametrize('name,value', [
     ('RC_TILE_CHUNK', '1'), ('RC_TILE_CHUNK', '99999'), ('RC_TILE_STATIC', '1001'),
-    ('RC_TILE_STATIC', 'ten'), ('RC_LANE_CHAIN', '2'), ('RC_LANE_CHAIN', ''),
+    ('RC_TILE_STATIC', 'ten'), ('RC_LANE_CHAIN', '2'), ('RC_LANE_CHAIN', ''), ('RC_LANE_CHAIN', 'lane'),
     ('RC_SEGMENT_EXT', '-1'), ('RC_PIPE_ALL', 'yes'), ('RC_OVERLAP_CUS', '0'),
     ('RC_TILE_GROUPS', 'on'), ('RC_SEGMENT_BYTES', '12abc'), ('RC_HOST_BATCH_BYTES', '15')])
 def test_malformed_knob_fails_creation(monkeypatch, name, value):
@@ -56,7 +56,7 @@ def test_malformed_knob_fails_creation(monkeypatch, name, value):
 
 
 @pytest.mark.parametrize('name,value', [
-    ('RC_TILE_CHUNK', '8'), ('RC_TILE_STATIC', '0x64'), ('RC_LANE_CHAIN', 'lane'),
+    ('RC_TILE_CHUNK', '8'), ('RC_TILE_STATIC', '0x64'), ('RC_LANE_CHAIN', '1'),
     ('RC_LANE_CHAIN', 'auto'), ('RC_PIPE_ALL', '1'), ('RC_B2_LANE_MAX', '-1'),
     ('RC_TILE_GROUPS', '0'), ('RC_SEGMENT_BYTES', '65536'), ('RC_HOST_BATCH_BYTES', '65536')])
 def test_legal_knob_passes(monkeypatch, name, value):
