@@ -81,6 +81,20 @@ int rc_gcm_encrypt_chunks(rc_gcm *g, const rc_chunker *layout, uint64_t n,
                           const uint64_t *d_cuts, const int64_t *d_counts, const uint8_t *d_keys,
                           const uint8_t *d_nonces, uint8_t *d_out, void *hip_stream);
 
+/* rc_gcm_encrypt_chunks for SELECTED chunks only, packed: cut slot c is encrypted when
+ * d_select[c] != 0 (one byte per cut slot; rc_index_resolve_chunks' d_fresh, replicat_index.h).
+ * The selected blobs lie back to back in cut-slot order from d_out + 0, without padding, each
+ * byte-identical to what rc_gcm_encrypt_chunks writes for that chunk with the same key and nonce
+ * (keys and nonces stay indexed by cut slot).  d_blob_off[c] receives the byte offset of slot
+ * c's blob in d_out, or ~0 when the slot holds no selected chunk; d_totals[0] the bytes written
+ * and d_totals[1] the number of blobs.  Counts and the selection are read on the device.
+ * d_out needs room for the selected blobs only (rc_gcm_chunks_layout bounds it).  Enqueued. */
+int rc_gcm_encrypt_chunks_select(rc_gcm *g, const rc_chunker *layout, uint64_t n,
+                                 const uint8_t *const *d_streams, const uint64_t *lens,
+                                 const uint64_t *d_cuts, const int64_t *d_counts, const uint8_t *d_keys,
+                                 const uint8_t *d_nonces, const uint8_t *d_select, uint8_t *d_out,
+                                 uint64_t *d_blob_off, uint64_t *d_totals, void *hip_stream);
+
 /* Kernel timing for benchmarks: while enabled, each enqueue records HIP events around its kernels
  * on the launch stream; read returns the summed milliseconds and clears. */
 int rc_gcm_timing_enable(rc_gcm *g, int enable);
@@ -135,6 +149,14 @@ int rc_chacha_encrypt_chunks(rc_chacha *g, const rc_chunker *layout, uint64_t n,
                              const uint8_t *const *d_streams, const uint64_t *lens,
                              const uint64_t *d_cuts, const int64_t *d_counts, const uint8_t *d_keys,
                              const uint8_t *d_nonces, uint8_t *d_out, void *hip_stream);
+
+/* As rc_gcm_encrypt_chunks_select, with 28 bytes of overhead per blob. */
+int rc_chacha_encrypt_chunks_select(rc_chacha *g, const rc_chunker *layout, uint64_t n,
+                                    const uint8_t *const *d_streams, const uint64_t *lens,
+                                    const uint64_t *d_cuts, const int64_t *d_counts,
+                                    const uint8_t *d_keys, const uint8_t *d_nonces,
+                                    const uint8_t *d_select, uint8_t *d_out, uint64_t *d_blob_off,
+                                    uint64_t *d_totals, void *hip_stream);
 
 int rc_chacha_timing_enable(rc_chacha *g, int enable);
 int rc_chacha_timing_read(rc_chacha *g, double *ms, uint64_t *calls);

@@ -29,6 +29,7 @@ RC_ERR_OVERFLOW = 13
 RC_ERR_NO_DEVICE = 14
 RC_ERR_DEVICE_FAULT = 15
 RC_ERR_CORRUPT = 16
+RC_ERR_INDEX_FULL = 17
 RC_COUNT_OVERFLOW = -1  # rc_chunk_device's per-stream counts besides the cut count
 RC_COUNT_FAULT = -3
 RC_OPEN = 1
@@ -39,8 +40,8 @@ RC_HASH_BLAKE2B, RC_HASH_SHA2, RC_HASH_SHA3 = 0, 1, 2
 RC_CIPHER_NONE, RC_CIPHER_AES_GCM, RC_CIPHER_CHACHA20_POLY1305 = 0, 1, 2
 RC_CHUNK_OK, RC_CHUNK_BAD_TAG, RC_CHUNK_CORRUPT = 0, 1, 2
 
-# every symbol include/replicat_chunker.h, replicat_digest.h, replicat_cipher.h and
-# replicat_restore.h declare:
+# every symbol include/replicat_chunker.h, replicat_digest.h, replicat_cipher.h,
+# replicat_restore.h and replicat_index.h declare:
 # name -> (restype, argtypes)
 _u64, _i64, _u32, _int, _p = ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p
 SIGNATURES = {
@@ -117,6 +118,7 @@ SIGNATURES = {
     'rc_gcm_decrypt_host': (_int, [_p, _u64, _p, _p, _p, _p, _p]),
     'rc_gcm_chunks_layout': (_u64, [_p, _p, _u64, _p, _p]),
     'rc_gcm_encrypt_chunks': (_int, [_p, _p, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'rc_gcm_encrypt_chunks_select': (_int, [_p, _p, _u64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     'rc_gcm_timing_enable': (_int, [_p, _int]),
     'rc_gcm_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
     'rc_chacha_create': (_int, [_int, ctypes.POINTER(_p)]),
@@ -129,6 +131,7 @@ SIGNATURES = {
     'rc_chacha_decrypt_host': (_int, [_p, _u64, _p, _p, _p, _p, _p]),
     'rc_chacha_chunks_layout': (_u64, [_p, _p, _u64, _p, _p]),
     'rc_chacha_encrypt_chunks': (_int, [_p, _p, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'rc_chacha_encrypt_chunks_select': (_int, [_p, _p, _u64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     'rc_chacha_timing_enable': (_int, [_p, _int]),
     'rc_chacha_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
     'rc_poly1305_host': (_int, [_u64, _p, _p, _p, _p]),
@@ -140,7 +143,16 @@ SIGNATURES = {
     'rc_restore_verify_host': (_int, [_p, _u64, _p, _p, _p, _p, _p]),
     'rc_restore_timing_enable': (_int, [_p, _int]),
     'rc_restore_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
+    # replicat_index.h
+    'rc_index_create': (_int, [_u32, _u64, _int, ctypes.POINTER(_p)]),
+    'rc_index_destroy': (None, [_p]),
+    'rc_index_name_bytes': (_u32, [_p]),
+    'rc_index_used': (_u64, [_p]),
+    'rc_index_add_host': (_int, [_p, _u64, _p, ctypes.POINTER(_u64)]),
+    'rc_index_resolve_chunks': (_int, [_p, _p, _u64, _p, _p, _p, ctypes.POINTER(_u64), _p, _p, _p]),
+    'rc_index_reserve': (_int, [_p, _u64]),
 }
+
 
 
 class ChunkerUnavailable(RuntimeError):
@@ -161,6 +173,11 @@ class ChunkCorrupted(ChunkerError):
 class ChunkerFault(ChunkerError):
     """The tile kernel took its fail-safe stop (RC_ERR_DEVICE_FAULT, RC_COUNT_FAULT): the call's
     cuts are not the reference's and must not be used."""
+
+
+class IndexFull(ChunkerError):
+    """A call would take a chunk-name index past its max_names (RC_ERR_INDEX_FULL): reserve()
+    more room first."""
 
 
 def check_counts(counts):
@@ -223,4 +240,6 @@ def check(code):
         raise ChunkerFault(code, msg)
     if code == RC_ERR_CORRUPT:
         raise ChunkCorrupted(code, msg)
+    if code == RC_ERR_INDEX_FULL:
+        raise IndexFull(code, msg)
     raise ChunkerError(code, msg)

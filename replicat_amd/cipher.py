@@ -215,6 +215,19 @@ class _GpuAead:
                                          lens.ctypes.data, cuts_ptr, counts_ptr, keys_ptr, nonces_ptr,
                                          out_ptr, stream or None))
 
+    def encrypt_chunks_select(self, chunker, ptrs, lens, cuts_ptr, counts_ptr, keys_ptr, nonces_ptr,
+                              select_ptr, out_ptr, blob_off_ptr, totals_ptr, stream=0):
+        """``encrypt_chunks`` for the chunks whose byte at select + c is non-zero (c: the cut
+        slot), packed: their blobs lie back to back in cut-slot order from out_ptr, each what
+        ``encrypt_chunks`` writes for that chunk; blob_off (uint64 per cut slot) receives each
+        blob's offset, or ~0 for a slot not selected, and totals (two uint64) the bytes written
+        and the number of blobs.  Counts and the selection are read on the device."""
+        ptrs, lens = _ptr_array(ptrs), _ptr_array(lens)
+        check(self._fn('encrypt_chunks_select')(self.handle(), chunker._h, len(lens), ptrs.ctypes.data,
+                                                lens.ctypes.data, cuts_ptr, counts_ptr, keys_ptr,
+                                                nonces_ptr, select_ptr, out_ptr, blob_off_ptr,
+                                                totals_ptr, stream or None))
+
     # ---------------------------------------------------------------------- profiling
 
     def timing(self, enable: bool):

@@ -101,6 +101,16 @@ int rc_chacha_encrypt_chunks(rc_chacha *g, const rc_chunker *layout, uint64_t n,
                           hip_stream);
 }
 
+int rc_chacha_encrypt_chunks_select(rc_chacha *g, const rc_chunker *layout, uint64_t n,
+                                    const uint8_t *const *d_streams, const uint64_t *lens,
+                                    const uint64_t *d_cuts, const int64_t *d_counts,
+                                    const uint8_t *d_keys, const uint8_t *d_nonces,
+                                    const uint8_t *d_select, uint8_t *d_out, uint64_t *d_blob_off,
+                                    uint64_t *d_totals, void *hip_stream) {
+    return encrypt_chunks_select(g, layout, n, d_streams, lens, d_cuts, d_counts, d_keys, d_nonces,
+                                 d_select, d_out, d_blob_off, d_totals, hip_stream);
+}
+
 int rc_chacha_timing_enable(rc_chacha *g, int enable) { return timing_enable(g, enable); }
 int rc_chacha_timing_read(rc_chacha *g, double *ms, uint64_t *calls) { return timing_read(g, ms, calls); }
 

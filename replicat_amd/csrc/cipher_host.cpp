@@ -370,6 +370,75 @@ int encrypt_chunks(CipherCore *g, const rc_chunker *layout, uint64_t n,
     return finish(*w, st);
 }
 
+int encrypt_chunks_select(CipherCore *g, const rc_chunker *layout, uint64_t n,
+                          const uint8_t *const *d_streams, const uint64_t *lens, const uint64_t *d_cuts,
+                          const int64_t *d_counts, const uint8_t *d_keys, const uint8_t *d_nonces,
+                          const uint8_t *d_select, uint8_t *d_out, uint64_t *d_blob_off,
+                          uint64_t *d_totals, void *hip_stream) {
+    if (!g || !layout) return rc_fail(RC_ERR_ARGUMENT, "null cipher or chunker");
+    if (!d_totals) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (n == 0) {
+        DeviceGuard guard(g->device);
+        RC_HIP_TRY(hipMemsetAsync(d_totals, 0, 2 * sizeof(uint64_t), st));
+        return RC_OK;
+    }
+    if (!d_streams || !lens || !d_cuts || !d_counts || !d_keys || !d_nonces || !d_select || !d_out ||
+        !d_blob_off)
+        return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    for (uint64_t i = 0; i < n; ++i) {
+        if (lens[i] && !d_streams[i])
+            return rc_fail(RC_ERR_ARGUMENT, "stream %llu: null pointer", (unsigned long long)i);
+        if (int rc = check_len(g->desc, i, lens[i])) return rc;  // a chunk is no longer than its stream
+    }
+    std::vector<uint64_t> caps(n);
+    const uint64_t total_cap = rc_cut_capacity(layout, n, lens, caps.data());
+    std::lock_guard<std::mutex> lock(g->mu);
+    DeviceGuard guard(g->device);
+    Workspace *w = nullptr;
+    if (int rc = acquire(g, w)) return rc;
+    // staging: [header 16 B] ptrs[n] cut_base[n] | device only: tile sums, items
+    const size_t up = 16 + 2 * n * sizeof(uint64_t);
+    const size_t items_off = up16(up + 2 * rc_gcm_select_tiles(total_cap) * sizeof(uint64_t));
+    if (int rc = w->h_stage.ensure(up)) return rc;
+    if (int rc = grow(w->d_stage, items_off + std::max<uint64_t>(total_cap, 1) * sizeof(GcmItem))) return rc;
+    uint8_t *h = static_cast<uint8_t *>(w->h_stage.p);
+    std::memset(h, 0, 16);
+    uint64_t *u = reinterpret_cast<uint64_t *>(h + 16);
+    uint64_t acc = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        u[i] = addr(d_streams[i]);
+        u[n + i] = acc;
+        acc += caps[i];
+    }
+    RC_HIP_TRY(hipMemcpyAsync(w->d_stage.p, h, up, hipMemcpyHostToDevice, st));
+    uint8_t *d = static_cast<uint8_t *>(w->d_stage.p);
+    const uint64_t *du = reinterpret_cast<const uint64_t *>(d + 16);
+    uint64_t *tile_sums = reinterpret_cast<uint64_t *>(d + up);
+    GcmItem *items = reinterpret_cast<GcmItem *>(d + items_off);
+    rc::PairTimer::Pair ev{};
+    if (int rc = g->timer.begin(st, ev)) return rc;
+    GcmSelectLists c{};
+    c.ptrs = du;
+    c.cut_base = du + n;
+    c.cuts = d_cuts;
+    c.counts = d_counts;
+    c.select = d_select;
+    c.n = n;
+    c.slots = total_cap;
+    c.keys = addr(d_keys);
+    c.nonces = addr(d_nonces);
+    c.out = addr(d_out);
+    c.nonce_bytes = g->desc.nonce_bytes;
+    // the work list holds d_totals[1] items (the selected chunks, on the device); the cipher
+    // kernel takes k < that over the bound total_cap, as on the unfiltered path
+    if (rc_gcm_launch_select_items(c, tile_sums, d_blob_off, d_totals, items, st))
+        return rc_fail(RC_ERR_HIP, "%s", rc_gcm_launch_error());
+    if (int rc = g->desc.launch(g, kEncrypt, items, d_totals + 1, total_cap, nullptr, st)) return rc;
+    if (int rc = g->timer.end(st, ev)) return rc;
+    return finish(*w, st);
+}
+
 int timing_enable(CipherCore *g, int enable) {
     if (int rc = check_handle(g)) return rc;
     g->timer.enabled = enable != 0;

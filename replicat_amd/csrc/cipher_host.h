@@ -102,6 +102,11 @@ int encrypt_chunks(CipherCore *g, const rc_chunker *layout, uint64_t n,
                    const uint8_t *const *d_streams, const uint64_t *lens, const uint64_t *d_cuts,
                    const int64_t *d_counts, const uint8_t *d_keys, const uint8_t *d_nonces,
                    uint8_t *d_out, void *hip_stream);
+int encrypt_chunks_select(CipherCore *g, const rc_chunker *layout, uint64_t n,
+                          const uint8_t *const *d_streams, const uint64_t *lens, const uint64_t *d_cuts,
+                          const int64_t *d_counts, const uint8_t *d_keys, const uint8_t *d_nonces,
+                          const uint8_t *d_select, uint8_t *d_out, uint64_t *d_blob_off,
+                          uint64_t *d_totals, void *hip_stream);
 int timing_enable(CipherCore *g, int enable);
 int timing_read(CipherCore *g, double *ms, uint64_t *calls);
 

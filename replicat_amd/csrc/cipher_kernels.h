@@ -43,3 +43,23 @@ struct GcmChunkLists {
 
 // Work list of the chunks: item chunk_off[i] + k = chunk k of stream i.
 int rc_gcm_launch_chunk_items(const GcmChunkLists &c, GcmItem *items, hipStream_t stream);
+
+// Chunk lists with a selection: select[s] != 0 marks the chunks (cut slots s, `slots` in all) to
+// encrypt; their blobs lie back to back from `out`.
+struct GcmSelectLists {
+    const uint64_t *ptrs, *cut_base, *cuts;
+    const int64_t *counts;
+    const uint8_t *select;
+    uint64_t n, slots;           // streams, cut slots of the layout
+    uint64_t keys, nonces, out;  // device addresses: 64-byte key slots, nonce_bytes per cut slot
+    uint32_t nonce_bytes;
+};
+
+// Tiles (workgroups) of the select passes over `slots` cut slots; tile_sums holds two words each.
+inline uint64_t rc_gcm_select_tiles(uint64_t slots) { return (slots + 1023) / 1024; }
+
+// The select scan and the select items: blob_off[s] = byte offset of slot s's blob (~0 if not
+// selected), items = the work list of the selected chunks in cut-slot order, totals = [bytes,
+// blobs].  tile_sums is scratch of 2 * rc_gcm_select_tiles(slots) words.
+int rc_gcm_launch_select_items(const GcmSelectLists &c, uint64_t *tile_sums, uint64_t *blob_off,
+                               uint64_t *totals, GcmItem *items, hipStream_t stream);

@@ -437,6 +437,140 @@ __global__ __launch_bounds__(256) void rc_gcm_items_kernel(GcmChunkLists c, GcmI
     }
 }
 
+// The stream of cut slot s: the last i with cut_base[i] <= s.
+__device__ __forceinline__ uint64_t stream_of_slot(const uint64_t *cut_base, uint64_t n, uint64_t s) {
+    uint64_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) / 2;
+        if (cut_base[mid] <= s)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// Blob length of cut slot s of stream i if it holds a selected chunk, else 0 (a blob is never
+// empty: it holds at least nonce and tag).
+__device__ __forceinline__ uint64_t selected_blob(const GcmSelectLists &c, uint64_t i, uint64_t s) {
+    const uint64_t k = s - c.cut_base[i];
+    const int64_t cnt = c.counts[i];
+    if (cnt <= 0 || k >= uint64_t(cnt) || !c.select[s]) return 0;
+    return c.cuts[s] - (k ? c.cuts[s - 1] : 0) + c.nonce_bytes + 16;
+}
+
+// Selected chunks only, packed: the exclusive scan over the cut slots of `selected ? len +
+// nonce_bytes + 16 : 0` (a blob's offset) and of `selected ? 1 : 0` (its place in the work list),
+// in two launches with a kernel boundary between them and no communication inside either.  A
+// tile is kSelectTile consecutive cut slots, four per lane.  (One workgroup walking every slot,
+// as rc_b2_scan_kernel walks the streams, took 1.2 ms for the 540 k cut slots of a 1 GiB batch of
+// 47 kB chunks -- as long as that batch's digests.)
+constexpr int kSelectThreads = 256, kSelectPerLane = 4, kSelectTile = kSelectThreads * kSelectPerLane;
+
+struct SelectLane {
+    uint64_t blob[kSelectPerLane];  // blob bytes of the lane's slots (0: not selected)
+    uint64_t bytes, blobs;          // their sums
+};
+
+__device__ __forceinline__ SelectLane select_lane(const GcmSelectLists &c, uint64_t s0) {
+    SelectLane l{};
+    if (s0 >= c.slots) return l;
+    uint64_t i = stream_of_slot(c.cut_base, c.n, s0);
+#pragma unroll
+    for (int j = 0; j < kSelectPerLane; ++j) {
+        const uint64_t s = s0 + j;
+        if (s >= c.slots) break;
+        while (i + 1 < c.n && c.cut_base[i + 1] <= s) ++i;
+        l.blob[j] = selected_blob(c, i, s);
+        l.bytes += l.blob[j];
+        l.blobs += l.blob[j] ? 1 : 0;
+    }
+    return l;
+}
+
+// Sum of (a, b) over the workgroup, in every lane.
+__device__ __forceinline__ void select_block_sum(uint64_t *sa, uint64_t *sb, uint64_t &a, uint64_t &b) {
+    sa[threadIdx.x] = a;
+    sb[threadIdx.x] = b;
+    __syncthreads();
+    for (int off = kSelectThreads / 2; off > 0; off >>= 1) {
+        if (int(threadIdx.x) < off) {
+            sa[threadIdx.x] += sa[threadIdx.x + off];
+            sb[threadIdx.x] += sb[threadIdx.x + off];
+        }
+        __syncthreads();
+    }
+    a = sa[0];
+    b = sb[0];
+    __syncthreads();
+}
+
+// Launch 1, the select scan's sums: tile_sums[2 t], [2 t + 1] = bytes and blobs selected in tile t.
+__global__ __launch_bounds__(kSelectThreads) void rc_gcm_select_scan_kernel(GcmSelectLists c,
+                                                                            uint64_t *__restrict__ tile_sums) {
+    __shared__ uint64_t sa[kSelectThreads], sb[kSelectThreads];
+    const SelectLane l = select_lane(c, uint64_t(blockIdx.x) * kSelectTile + threadIdx.x * kSelectPerLane);
+    uint64_t a = l.bytes, b = l.blobs;
+    select_block_sum(sa, sb, a, b);
+    if (threadIdx.x == 0) {
+        tile_sums[2 * uint64_t(blockIdx.x)] = a;
+        tile_sums[2 * uint64_t(blockIdx.x) + 1] = b;
+    }
+}
+
+// Launch 2, the select items: a tile's base is the sum of the tiles before it; within the tile an
+// exclusive scan over the lanes; blob_off[s] (~0 where slot s is not selected), the work list in
+// cut-slot order, and (the last tile) totals = [bytes, blobs].
+__global__ __launch_bounds__(kSelectThreads) void rc_gcm_select_items_kernel(GcmSelectLists c,
+                                                                             const uint64_t *__restrict__ tile_sums,
+                                                                             uint64_t *__restrict__ blob_off,
+                                                                             uint64_t *__restrict__ totals,
+                                                                             GcmItem *__restrict__ items) {
+    __shared__ uint64_t sa[kSelectThreads], sb[kSelectThreads];
+    uint64_t base = 0, first = 0;
+    for (uint64_t t = threadIdx.x; t < blockIdx.x; t += kSelectThreads) {
+        base += tile_sums[2 * t];
+        first += tile_sums[2 * t + 1];
+    }
+    select_block_sum(sa, sb, base, first);
+    const uint64_t s0 = uint64_t(blockIdx.x) * kSelectTile + threadIdx.x * kSelectPerLane;
+    const SelectLane l = select_lane(c, s0);
+    sa[threadIdx.x] = l.bytes;
+    sb[threadIdx.x] = l.blobs;
+    __syncthreads();
+    for (int off = 1; off < kSelectThreads; off <<= 1) {  // inclusive Hillis-Steele scan
+        const uint64_t v = int(threadIdx.x) >= off ? sa[threadIdx.x - off] : 0;
+        const uint64_t u = int(threadIdx.x) >= off ? sb[threadIdx.x - off] : 0;
+        __syncthreads();
+        sa[threadIdx.x] += v;
+        sb[threadIdx.x] += u;
+        __syncthreads();
+    }
+    uint64_t off = base + sa[threadIdx.x] - l.bytes, ord = first + sb[threadIdx.x] - l.blobs;
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == kSelectThreads - 1) {
+        totals[0] = base + sa[kSelectThreads - 1];
+        totals[1] = first + sb[kSelectThreads - 1];
+    }
+    if (s0 >= c.slots) return;
+    uint64_t i = stream_of_slot(c.cut_base, c.n, s0);
+#pragma unroll
+    for (int j = 0; j < kSelectPerLane; ++j) {
+        const uint64_t s = s0 + j;
+        if (s >= c.slots) break;
+        if (!l.blob[j]) {
+            blob_off[s] = ~uint64_t(0);
+            continue;
+        }
+        while (i + 1 < c.n && c.cut_base[i + 1] <= s) ++i;
+        const uint64_t k = s - c.cut_base[i], start = k ? c.cuts[s - 1] : 0;
+        blob_off[s] = off;
+        items[ord] = GcmItem{c.ptrs[i] + start, c.cuts[s] - start, c.out + off, c.keys + 64 * s,
+                             c.nonces + c.nonce_bytes * s, s};
+        off += l.blob[j];
+        ++ord;
+    }
+}
+
 namespace {
 thread_local char g_gcm_err[256];
 
@@ -490,4 +624,14 @@ int rc_gcm_launch_chunk_items(const GcmChunkLists &c, GcmItem *items, hipStream_
     const unsigned groups = static_cast<unsigned>((c.n + c.spw - 1) / c.spw);
     rc_gcm_items_kernel<<<groups, 256, 0, stream>>>(c, items);
     return gcm_status("rc_gcm_items_kernel");
+}
+
+int rc_gcm_launch_select_items(const GcmSelectLists &c, uint64_t *tile_sums, uint64_t *blob_off,
+                               uint64_t *totals, GcmItem *items, hipStream_t stream) {
+    if (!c.n || !c.slots) return 0;
+    const unsigned tiles = static_cast<unsigned>(rc_gcm_select_tiles(c.slots));
+    rc_gcm_select_scan_kernel<<<tiles, kSelectThreads, 0, stream>>>(c, tile_sums);
+    if (gcm_status("rc_gcm_select_scan_kernel")) return 1;
+    rc_gcm_select_items_kernel<<<tiles, kSelectThreads, 0, stream>>>(c, tile_sums, blob_off, totals, items);
+    return gcm_status("rc_gcm_select_items_kernel");
 }

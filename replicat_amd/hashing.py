@@ -188,15 +188,19 @@ class GpuBlake2b(_GpuHasher):
         return state_init(self.digest_size, key=key, salt=salt, person=person)
 
     def derive_chunks(self, chunker, lens, counts_ptr, kdf_state_ptr, digests_ptr, keys_ptr,
-                      stream=0):
+                      stream=0, msg_len=None):
         """Enqueue ``derive_shared_subkey(digest)`` of every chunk digest ``digest_chunks`` left
         in HBM (repository.py:132-137, 1470-1472; adapters.py:205-213): the device state at
         kdf_state_ptr -- ``state_init(key_bytes, key=shared_key, salt=shared_kdf_params)``, only
-        read -- absorbs the digest of cut slot s and its digest lands at keys + 64 s."""
+        read -- absorbs the digest of cut slot s and its digest lands at keys + 64 s.  The same
+        call names chunks (naming.py: the state is the MAC's, ``state_init(L, key=mac_key)``):
+        msg_len is then the bytes absorbed from each slot (default: this hasher's digest size),
+        and the output size is the state's."""
         lens = _ptr_array(lens)
         check(lib().rc_blake2b_derive_chunks(self._h, chunker._h, len(lens), lens.ctypes.data,
                                              counts_ptr, kdf_state_ptr, digests_ptr,
-                                             self.digest_size, keys_ptr, stream or None))
+                                             self.digest_size if msg_len is None else int(msg_len),
+                                             keys_ptr, stream or None))
 
 
 class _GpuSha(_GpuHasher):

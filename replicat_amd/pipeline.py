@@ -22,7 +22,10 @@ incremental digests of small files (rc_blake2b_update_device: each file's bytes 
 the batch that first holds them; a file's state lives in HBM across batches) and, with ``encryption``, every
 chunk's subkey (rc_blake2b_derive_chunks) and its AES-GCM encryption (rc_gcm_encrypt_chunks).
 Only cut offsets, digests and -- what replicat uploads -- the chunk contents come back: sliced
-from the host batch, or the device's nonce || C || T when encrypted.
+from the host batch, or the device's nonce || C || T when encrypted.  With ``naming`` the chunk's
+name and tag (its location, repository.py:470-481) come back too, and with an ``index`` of the
+names the repository holds (dedup.GpuChunkIndex) only chunks that are new are encrypted and
+copied back (rc_index_resolve_chunks, rc_*_encrypt_chunks_select).
 
 Memory held per producer: ``slots`` x (one pinned host batch + its HBM copy) of ``capacity`` =
 batch_bytes + max_length + 16 MiB + 128 bytes each (~1.02 GiB at the default 1 GiB batch, so ~2.1
@@ -70,6 +73,7 @@ from .chunker import (MAX_LENGTH, MIN_LENGTH, GpuChunker, QueueStream, _current_
                       check_counts, normalize_params)
 from .hashing import (SHA_BITS, SLOT, GpuBlake2b, hasher_from_config, hashlib_from_config,
                       initial_state_from_config, state_init)
+from .naming import ChunkNaming, chunk_location
 from .snapshot import PIECE, PieceReader, file_parts, sort_files
 
 # The device time of a batch has a floor: the BLAKE2b chain of its longest chunk (~55 ms for a
@@ -130,10 +134,16 @@ class _Lease:
 
 @dataclass
 class ChunkRecord:
-    """repository.py:1477-1485 (_SnapshotChunk) without the upload location.  ``contents`` is
-    what replicat uploads: the chunk bytes, or nonce || C || T for an encrypted repository --
-    bytes from run(), a read-only memoryview into the producer's pinned batch from stream()
-    (valid until release())."""
+    """repository.py:1477-1485 (_SnapshotChunk); the upload location only with the producer's
+    ``naming``.  ``contents`` is what replicat uploads: the chunk bytes, or nonce || C || T for an
+    encrypted repository -- bytes from run(), a read-only memoryview into the producer's pinned
+    batch from stream() (valid until release()).
+
+    With ``naming``: ``name`` and ``tag`` (bytes; repository.py:470-477) and ``location``.  With
+    an ``index`` too: ``known`` -- the index held the name before this run -- and ``first``, the
+    counter of the chunk's first occurrence in this run (None when known).  A record that is
+    neither known nor its own first occurrence is a duplicate within the snapshot; only first
+    occurrences of unknown chunks carry ``contents``."""
     counter: int
     stream_start: int
     stream_end: int
@@ -141,6 +151,17 @@ class ChunkRecord:
     table_index: int
     contents: Optional[object] = field(default=None, repr=False)
     _lease: Optional[_Lease] = field(default=None, repr=False, compare=False)
+    name: Optional[bytes] = None
+    tag: Optional[bytes] = None
+    known: Optional[bool] = None
+    first: Optional[int] = None
+
+    @property
+    def location(self) -> Optional[str]:
+        """_chunk_digest_to_location (repository.py:479-481), built on access."""
+        if self.name is None:
+            return None
+        return chunk_location(self.name.hex(), self.tag.hex())
 
     def release(self):
         """Done with ``contents`` (a stream() record): its batch buffer may be refilled.
@@ -363,11 +384,29 @@ class _Slot:
             # the shared-subkey KDF is BLAKE2b whatever the hasher is; it absorbs digest_size bytes
             self.kdf_hasher = GpuBlake2b(length=prod.digest_size, device=prod.device)
             self.cipher = prod.encryption.make_cipher(prod.device)
+        if prod.naming is not None and prod.naming.keyed:
+            total = max(prod.cut_cap, 1)
+            self.d_names = torch.zeros((total, SLOT), dtype=torch.uint8, device=dev)
+            self.d_tags = torch.zeros((total, SLOT), dtype=torch.uint8, device=dev)
+            self.mac_hasher = GpuBlake2b(length=prod.naming.length, device=prod.device)
+        if prod.index is not None:
+            total = max(prod.cut_cap, 1)
+            self.d_owner = torch.zeros(total, dtype=torch.int64, device=dev)
+            self.d_fresh = torch.zeros(total, dtype=torch.uint8, device=dev)
+            self.h_owner = torch.zeros(total, dtype=torch.int64, pin_memory=True)
+            self.h_fresh = torch.zeros(total, dtype=torch.uint8, pin_memory=True)
+            self.ev_index = torch.cuda.Event()
+            self.id_base = 0
+            if prod.encryption is not None:
+                self.d_blob_off = torch.zeros(total, dtype=torch.int64, device=dev)
+                self.h_blob_off = torch.zeros(total, dtype=torch.int64, pin_memory=True)
+                self.d_totals = torch.zeros(2, dtype=torch.int64, device=dev)
+                self.h_totals = torch.zeros(2, dtype=torch.int64, pin_memory=True)
         self.lease = _Lease()  # stream(): records still viewing host / h_enc
         self.reset(prod.head)
 
     def close(self):
-        for h in ('hasher', 'file_hasher', 'kdf_hasher', 'cipher'):
+        for h in ('hasher', 'file_hasher', 'kdf_hasher', 'mac_hasher', 'cipher'):
             obj = getattr(self, h, None)
             if obj is not None and hasattr(obj, 'close'):
                 obj.close()
@@ -389,7 +428,26 @@ class _Slot:
 
 class DeviceSnapshotProducer:
     """Chunks, chunk digests, file digests and (optionally) encrypted chunks of a snapshot's
-    stream on one HIP device."""
+    stream on one HIP device.
+
+    ``naming`` (a naming.ChunkNaming) adds every chunk's name, tag and location
+    (repository.py:470-481), computed on the device after the chunk digests.  With ``index`` (a
+    dedup.GpuChunkIndex holding the names the repository already has, e.g. from a listing of
+    ``data/``) the producer also asks, per batch and before any cipher work, whether each chunk
+    is new: records carry ``known`` and ``first``, and only the first occurrence of an unknown
+    chunk is encrypted, copied back and given ``contents`` (run() and stream() alike).  With both
+    None nothing changes.
+
+    * After a run the index also holds that run's names: a later run on the same index reports
+      them as known.  Whether that is true of the repository (did the uploads succeed?) is the
+      caller's to decide; a fresh index from a fresh listing is always right.
+    * A duplicate's first occurrence may not have been uploaded yet when the consumer sees the
+      duplicate (the reference has the same window: it notices duplicates at upload time).
+    * For an unencrypted repository the contents never leave the host batch, so the filter saves
+      no transfer; it still reports ``known`` and ``first``.
+    * One index belongs to one device; merging indices across ranks is not provided.  Batches
+      resolve in stream order (an event chain), so "first" is first in the stream; the index
+      grows (doubling, a blocking ``reserve``) before a batch that could overflow it."""
 
     def __init__(self, *, min_length: int = MIN_LENGTH, max_length: int = MAX_LENGTH,
                  params: Optional[bytes] = None, digest_size: Optional[int] = None,
@@ -397,9 +455,19 @@ class DeviceSnapshotProducer:
                  encryption: Optional[ChunkEncryption] = None, file_digests: str = 'auto',
                  slots: int = 3, queues: str = 'own', read_threads: int = 4,
                  timeline: bool = False, hashing: str = 'blake2b',
-                 hash_bits: Optional[int] = None):
+                 hash_bits: Optional[int] = None, naming: Optional[ChunkNaming] = None,
+                 index=None):
         digest_size, hash_bits, self._hash_args = hashing_arguments(hashing, digest_size, hash_bits)
         self.hashing, self.hash_bits = hashing, hash_bits
+        # naming: names, tags and locations on the records; with index (a dedup.GpuChunkIndex of
+        # the names the repository holds) only new chunks are encrypted and copied back
+        if index is not None and naming is None:
+            raise ValueError('index needs naming: the index holds chunk names')
+        self.naming, self.index = naming, index
+        self.name_bytes = naming.name_bytes(digest_size) if naming is not None else 0
+        if index is not None and index.name_bytes != self.name_bytes:
+            raise ValueError(f'naming gives {self.name_bytes}-byte names, the index holds '
+                             f'{index.name_bytes}-byte names')
         import torch
         if device is None:
             device = _current_device()
@@ -439,6 +507,12 @@ class DeviceSnapshotProducer:
                                          dtype=np.uint8)
         self.HOST_DIGEST_MIN = self.HOST_DIGEST_MIN_BY_HASH[hashing, hash_bits]
         self.encryption = encryption
+        if index is not None and index.device != self.device:
+            raise ValueError(f'the index lives on device {index.device}, the producer on {self.device}')
+        if naming is not None and naming.keyed:
+            # the MAC's state: it absorbs a digest (then a name) per chunk, as the KDF's does
+            mac = state_init(naming.length, key=naming.mac_key)
+            self.d_mac = torch.from_numpy(np.frombuffer(mac, dtype=np.uint8).copy()).to(self.dev)
         if encryption is not None:
             # the layout of the ciphertexts (nonce || C || T per chunk); each slot encrypts with
             # its own handle
@@ -580,7 +654,8 @@ class DeviceSnapshotProducer:
         # host_digest_wait: the collector thread (overlapping the next fill)
         prof = self.profile = {'fill': 0.0, 'wait_cut': 0.0, 'enqueue': 0.0, 'collect_join': 0.0,
                                'collect_wait': 0.0, 'records': 0.0, 'host_digest_wait': 0.0,
-                               'release_wait': 0.0, 'batches': 0, 't0': time.perf_counter()}
+                               'release_wait': 0.0, 'batches': 0, 't0': time.perf_counter(),
+                               'enc_bytes_copied': 0, 'chunks_skipped': 0}
         clock = time.perf_counter
         prev, look, k = None, None, 0
         # records are built on a collector thread (they copy chunk contents, holding the GIL)
@@ -671,6 +746,12 @@ class _Run:
         self.hstates = {}    # file index -> _HostHash (host-engine files)
         self.engine = {}     # file index -> its digest runs on the host (decided once)
         self.finalized = 0   # files [0, finalized) have their digest
+        # with an index: ids below id0 were in it before this run (known chunks); first_of maps
+        # the id of a chunk that was new to the counter of its record; last_index is the slot
+        # whose resolve call the next one waits for
+        self.id0 = prod.index.used if prod.index is not None else 0
+        self.first_of: Dict[int, int] = {}
+        self.last_index = None
 
     def host_piece(self, s, fi, at, n):
         """A file piece just placed at s.hnp[at:at + n]: hashed now on a host thread if the
@@ -739,6 +820,28 @@ class _Run:
             s.ev_upd.record(s.stream)
             s.hasher.digest_chunks(p.chunker, [ptr], [s.blen], s.d_cuts.data_ptr(),
                                    s.d_count.data_ptr(), s.d_digests.data_ptr(), hs)
+            if p.naming is not None and p.naming.keyed:
+                # name = mac(digest), tag = mac(name) (repository.py:470-477): the subkeys'
+                # kernel with the MAC's state, over the digests and then over the names
+                for src, dst, n_in in ((s.d_digests, s.d_names, p.digest_size),
+                                       (s.d_names, s.d_tags, p.name_bytes)):
+                    s.mac_hasher.derive_chunks(p.chunker, [s.blen], s.d_count.data_ptr(),
+                                               p.d_mac.data_ptr(), src.data_ptr(), dst.data_ptr(),
+                                               hs, msg_len=n_in)
+            if p.index is not None:
+                # new or known?  Index calls are ordered batch after batch (an event chain like
+                # ev_upd's), so "first occurrence" is first in stream order
+                if self.last_index is not None:
+                    s.stream.wait_event(self.last_index.ev_index)
+                p.index.ensure_room(p.cut_cap)
+                names = s.d_names if p.naming.keyed else s.d_digests
+                s.id_base = p.index.resolve_chunks(p.chunker, [s.blen], s.d_count.data_ptr(),
+                                                   names.data_ptr(), s.d_owner.data_ptr(),
+                                                   s.d_fresh.data_ptr(), hs)
+                s.ev_index.record(s.stream)
+                self.last_index = s
+                s.h_owner.copy_(s.d_owner, non_blocking=True)
+                s.h_fresh.copy_(s.d_fresh, non_blocking=True)
             if p.encryption is not None:
                 # derive_shared_subkey(digest) and encrypt, per chunk, still in HBM; one
                 # os.urandom nonce per chunk as the adapter draws them (adapters.py:133)
@@ -748,9 +851,17 @@ class _Run:
                 s.h_nonces.numpy()[:] = np.frombuffer(os.urandom(s.h_nonces.numel()),
                                                       dtype=np.uint8)
                 s.d_nonces.copy_(s.h_nonces, non_blocking=True)
-                s.cipher.encrypt_chunks(p.chunker, [ptr], [s.blen], s.d_cuts.data_ptr(),
-                                        s.d_count.data_ptr(), s.d_keys.data_ptr(),
-                                        s.d_nonces.data_ptr(), s.d_enc.data_ptr(), hs)
+                if p.index is not None:  # first occurrences of unknown chunks only, packed
+                    s.cipher.encrypt_chunks_select(
+                        p.chunker, [ptr], [s.blen], s.d_cuts.data_ptr(), s.d_count.data_ptr(),
+                        s.d_keys.data_ptr(), s.d_nonces.data_ptr(), s.d_fresh.data_ptr(),
+                        s.d_enc.data_ptr(), s.d_blob_off.data_ptr(), s.d_totals.data_ptr(), hs)
+                    s.h_blob_off.copy_(s.d_blob_off, non_blocking=True)
+                    s.h_totals.copy_(s.d_totals, non_blocking=True)
+                else:
+                    s.cipher.encrypt_chunks(p.chunker, [ptr], [s.blen], s.d_cuts.data_ptr(),
+                                            s.d_count.data_ptr(), s.d_keys.data_ptr(),
+                                            s.d_nonces.data_ptr(), s.d_enc.data_ptr(), hs)
             s.ev_done.record(s.stream)
 
     def collect(self, s):
@@ -768,10 +879,24 @@ class _Run:
             digs = s.d_digests[:count, :p.digest_size].cpu().numpy()
             fd = (s.file_digests[:, :p.digest_size].cpu().numpy()
                   if s.file_digests is not None else None)
+            names = tags = None
+            if p.naming is not None and p.naming.keyed:
+                names = s.d_names[:count, :p.name_bytes].cpu().numpy()
+                tags = s.d_tags[:count, :p.name_bytes].cpu().numpy()
+        owners = fresh = blob_off = None
+        if p.index is not None:  # in pinned memory since ev_done
+            owners = s.h_owner[:count].numpy()
+            p.index.check_owners(owners)
+            owners, fresh = owners.tolist(), s.h_fresh[:count].numpy().tolist()
         enc = over = None
         if p.encryption is not None:
             over = p.cipher.nonce_bytes + 16
-            n_out = (int(ends[-1]) if count else 0) + count * over
+            if p.index is not None:
+                n_out = int(s.h_totals[0])  # exactly the selected blobs
+                blob_off = s.h_blob_off[:count].numpy().tolist()
+            else:
+                n_out = (int(ends[-1]) if count else 0) + count * over
+            prof['enc_bytes_copied'] += n_out
             with torch.cuda.stream(s.stream):
                 s.h_enc[:n_out].copy_(s.d_enc[:n_out], non_blocking=True)
             s.stream.synchronize()
@@ -798,32 +923,50 @@ class _Run:
         # zero copy: read-only views into the pinned batch (or ciphertexts), leased per batch
         view = memoryview(enc if enc is not None else hnp).toreadonly() if zc else None
         out = [] if self.sink is not None else None
-        prev = 0
+        prev = leased = 0
+        name = tag = known = first = None
         for k, e in enumerate(ends.tolist()):
             d = digs[k].tobytes()
             idx = table.get(d)
             if idx is None:
                 idx = table[d] = len(table)
-            if enc is not None:  # nonce || C || T of chunk k at prev + k (nonce_bytes + 16)
-                o = prev + k * over
+            counter = len(chunks) + 1
+            if p.naming is not None:
+                name, tag = (names[k].tobytes(), tags[k].tobytes()) if names is not None else (d, d)
+            wanted = True
+            if owners is not None:  # cut slot k of the batch's one stream has id id_base + k
+                known = owners[k] < self.id0
+                if fresh[k]:
+                    first = self.first_of[s.id_base + k] = counter
+                else:
+                    first = None if known else self.first_of[owners[k]]
+                    wanted = False
+                    prof['chunks_skipped'] += 1
+            if not wanted:
+                contents = None
+            elif enc is not None:  # nonce || C || T of chunk k at prev + k (nonce_bytes + 16)
+                o = prev + k * over if blob_off is None else blob_off[k]
                 contents = view[o:o + (e - prev) + over] if zc else enc[o:o + (e - prev) + over].tobytes()
             elif not p.keep_contents:
                 contents = None
             else:
                 contents = view[s.off + prev:s.off + e] if zc else hnp[s.off + prev:s.off + e].tobytes()
-            rec = ChunkRecord(counter=len(chunks) + 1, stream_start=s.buf_start + prev,
+            rec = ChunkRecord(counter=counter, stream_start=s.buf_start + prev,
                               stream_end=s.buf_start + e, digest=d, table_index=idx,
-                              contents=None if zc else contents)
+                              contents=None if zc else contents, name=name, tag=tag, known=known,
+                              first=first)
             chunks.append(rec)
             if out is not None:
-                if zc:  # the consumer's copy of the record carries the view and the lease
+                if zc:  # the consumer's copy of the record carries the view and, with it, the lease
+                    lease = s.lease if contents is not None else None
+                    leased += lease is not None
                     rec = ChunkRecord(rec.counter, rec.stream_start, rec.stream_end, d, idx,
-                                      contents, s.lease)
+                                      contents, lease, name, tag, known, first)
                 out.append(rec)
             prev = e
         if out is not None:
             if zc:
-                s.lease.take(len(out))
+                s.lease.take(leased)
             self.sink(out)
         t2 = clock()
         prof['records'] += t2 - t1
@@ -964,4 +1107,4 @@ def snapshot_stream(paths, **kw) -> SnapshotStream:
 
 
 __all__ = ['DeviceSnapshotProducer', 'SnapshotStream', 'ChunkStream', 'FileRecord', 'ChunkRecord',
-           'ChunkEncryption', 'snapshot_stream', 'DEFAULT_BATCH']
+           'ChunkEncryption', 'ChunkNaming', 'snapshot_stream', 'DEFAULT_BATCH']
