@@ -65,6 +65,25 @@ int rc_index_resolve_chunks(rc_index *idx, const rc_chunker *layout, uint64_t n,
                             uint64_t *id_base, int64_t *d_owner, uint8_t *d_fresh,
                             void *hip_stream);
 
+/* The same for n names that are not a chunker's output: a flat array, d_names + 64 i for
+ * i < n, every one a name.  Takes the n ids *id_base + i; d_owner[i] and d_fresh[i] as above.
+ * RC_ERR_INDEX_FULL, before anything is enqueued and with the index unchanged, when used + n
+ * exceeds max_names. */
+int rc_index_resolve_names_device(rc_index *idx, uint64_t n, const uint8_t *d_names,
+                                  uint64_t *id_base, int64_t *d_owner, uint8_t *d_fresh,
+                                  void *hip_stream);
+
+#define RC_INDEX_ABSENT (-1)    /* rc_index_lookup_device: no id carries the name */
+#define RC_INDEX_EXHAUSTED (-2) /* rc_index_lookup_device: the probe bound ran out (a full table) */
+
+/* Read-only: d_owner[i] = the smallest id that carries the name at d_names + 64 i (the first
+ * name_bytes bytes count), RC_INDEX_ABSENT if none does, RC_INDEX_EXHAUSTED if the probe bound
+ * was exhausted (never at the load the index keeps; the reader treats it as an error).  Takes no
+ * id, pools and inserts nothing: rc_index_used and every later owner are what they were.
+ * Enqueued on hip_stream, no synchronisation. */
+int rc_index_lookup_device(rc_index *idx, uint64_t n, const uint8_t *d_names, int64_t *d_owner,
+                           void *hip_stream);
+
 /* Room for max_names ids (no-op when there is that much).  Blocking: waits for the index's
  * outstanding work, allocates the larger pool and table, copies the pool and re-inserts every
  * table entry.  Ids and owners are unchanged. */

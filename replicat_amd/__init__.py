@@ -8,3 +8,15 @@ hand-written gfx950 HIP kernels in ``libreplicat_chunker.so`` behind a C ABI
 many device- or host-resident streams (``replicat_amd.chunker``).
 """
 __version__ = '0.3.0'
+
+_GC_EXPORTS = ('GpuChunkGC', 'CleanPlan')
+__all__ = list(_GC_EXPORTS)
+
+
+def __getattr__(name):
+    # garbage-collection planning (replicat_amd/gc.py), imported on first use: the package itself
+    # stays importable without numpy
+    if name in _GC_EXPORTS:
+        from . import gc
+        return getattr(gc, name)
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

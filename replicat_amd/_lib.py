@@ -30,6 +30,9 @@ RC_ERR_NO_DEVICE = 14
 RC_ERR_DEVICE_FAULT = 15
 RC_ERR_CORRUPT = 16
 RC_ERR_INDEX_FULL = 17
+RC_ERR_PROBE_BOUND = 18
+RC_INDEX_ABSENT, RC_INDEX_EXHAUSTED = -1, -2  # rc_index_lookup_device's owners besides an id
+RC_GC_REFERENCED, RC_GC_DELETE, RC_GC_TAG_MISMATCH, RC_GC_EXHAUSTED = 0, 1, 2, 3
 RC_COUNT_OVERFLOW = -1  # rc_chunk_device's per-stream counts besides the cut count
 RC_COUNT_FAULT = -3
 RC_OPEN = 1
@@ -41,7 +44,7 @@ RC_CIPHER_NONE, RC_CIPHER_AES_GCM, RC_CIPHER_CHACHA20_POLY1305 = 0, 1, 2
 RC_CHUNK_OK, RC_CHUNK_BAD_TAG, RC_CHUNK_CORRUPT = 0, 1, 2
 
 # every symbol include/replicat_chunker.h, replicat_digest.h, replicat_cipher.h,
-# replicat_restore.h and replicat_index.h declare:
+# replicat_restore.h, replicat_index.h and replicat_gc.h declare:
 # name -> (restype, argtypes)
 _u64, _i64, _u32, _int, _p = ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p
 SIGNATURES = {
@@ -151,6 +154,21 @@ SIGNATURES = {
     'rc_index_add_host': (_int, [_p, _u64, _p, ctypes.POINTER(_u64)]),
     'rc_index_resolve_chunks': (_int, [_p, _p, _u64, _p, _p, _p, ctypes.POINTER(_u64), _p, _p, _p]),
     'rc_index_reserve': (_int, [_p, _u64]),
+    'rc_index_lookup_device': (_int, [_p, _u64, _p, _p, _p]),
+    'rc_index_resolve_names_device': (_int, [_p, _u64, _p, ctypes.POINTER(_u64), _p, _p, _p]),
+    # replicat_gc.h
+    'rc_gc_create': (_int, [_u32, _u32, _p, _u32, _u64, _int, ctypes.POINTER(_p)]),
+    'rc_gc_destroy': (None, [_p]),
+    'rc_gc_name_bytes': (_u32, [_p]),
+    'rc_gc_used': (_u64, [_p]),
+    'rc_gc_capacity': (_u64, [_p]),
+    'rc_gc_reference_host': (_int, [_p, _u64, _p]),
+    'rc_gc_sweep_device': (_int, [_p, _u64, _p, _p, _u64, _p, _p, _p, _p]),
+    'rc_gc_sweep_host': (_int, [_p, _u64, _p, _p, _p, _p, ctypes.POINTER(_u64)]),
+    'rc_gc_unreferenced_host': (_int, [_p, _u64, _p, _p, _p, _p, ctypes.POINTER(_u64)]),
+    'rc_gc_timing_enable': (_int, [_p, _int]),
+    'rc_gc_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                 ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
 }
 
 

@@ -183,6 +183,45 @@ int rc_index_resolve_chunks(rc_index *x, const rc_chunker *layout, uint64_t n, c
     return RC_OK;
 }
 
+int rc_index_lookup_device(rc_index *x, uint64_t n, const uint8_t *d_names, int64_t *d_owner,
+                           void *hip_stream) {
+    if (!x) return rc_fail(RC_ERR_ARGUMENT, "null index");
+    if (n == 0) return RC_OK;
+    if (!d_names || !d_owner) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    if (reinterpret_cast<uintptr_t>(d_names) & 7)
+        return rc_fail(RC_ERR_ALIGN, "d_names is not 8-byte aligned");
+    std::lock_guard<std::mutex> lock(x->mu);
+    rc::DeviceGuard guard(x->device);
+    if (rc_index_launch_lookup(view_of(x), n, d_names, d_owner, static_cast<hipStream_t>(hip_stream)))
+        return rc_fail(RC_ERR_HIP, "%s", rc_index_launch_error());
+    return RC_OK;
+}
+
+int rc_index_resolve_names_device(rc_index *x, uint64_t n, const uint8_t *d_names, uint64_t *id_base,
+                                  int64_t *d_owner, uint8_t *d_fresh, void *hip_stream) {
+    if (!x) return rc_fail(RC_ERR_ARGUMENT, "null index");
+    if (!id_base) return rc_fail(RC_ERR_ARGUMENT, "null id_base");
+    if (n == 0) {
+        *id_base = x->used;
+        return RC_OK;
+    }
+    if (!d_names || !d_owner || !d_fresh) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    if (reinterpret_cast<uintptr_t>(d_names) & 7)
+        return rc_fail(RC_ERR_ALIGN, "d_names is not 8-byte aligned");
+    std::lock_guard<std::mutex> lock(x->mu);
+    *id_base = x->used;
+    if (int rc = check_room(x, n)) return rc;
+    rc::DeviceGuard guard(x->device);
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const IndexView v = view_of(x);
+    const IndexWork work{nullptr, nullptr, 0, n, x->used};  // flat: every lane carries a name
+    if (rc_index_launch_stage(v, work, d_names, st) || rc_index_launch_insert(v, work, st) ||
+        rc_index_launch_resolve(v, work, d_owner, d_fresh, st))
+        return rc_fail(RC_ERR_HIP, "%s", rc_index_launch_error());
+    x->used += n;
+    return RC_OK;
+}
+
 int rc_index_reserve(rc_index *x, uint64_t max_names) {
     if (!x) return rc_fail(RC_ERR_ARGUMENT, "null index");
     if (max_names > (uint64_t(1) << 40)) return rc_fail(RC_ERR_ARGUMENT, "max_names above 2^40");
@@ -215,3 +254,10 @@ int rc_index_reserve(rc_index *x, uint64_t max_names) {
 }
 
 }  // extern "C"
+
+int rc_index_view(rc_index *x, IndexView *out) {
+    if (!x || !out) return rc_fail(RC_ERR_ARGUMENT, "null index");
+    std::lock_guard<std::mutex> lock(x->mu);
+    *out = view_of(x);
+    return RC_OK;
+}

@@ -14,6 +14,7 @@
 #include <cstdio>
 
 #include "index_kernels.h"
+#include "index_lookup.h"
 
 namespace {
 
@@ -110,6 +111,19 @@ __global__ __launch_bounds__(kIndexThreads) void rc_index_resolve_kernel(IndexVi
     fresh[s] = found == int64_t(id) ? 1 : 0;
 }
 
+// The id already in the index for each of n caller names (64-byte slots), kIndexAbsent or
+// kIndexExhausted.  Nothing is pooled or inserted; reaching an empty entry is the normal answer
+// for a name nobody holds, which is why it is told apart from an exhausted probe bound here.
+__global__ __launch_bounds__(kIndexThreads) void rc_index_lookup_kernel(IndexView v, uint64_t n,
+                                                                        const uint8_t *names,
+                                                                        int64_t *owner) {
+    const uint64_t i = uint64_t(blockIdx.x) * kIndexThreads + threadIdx.x;
+    if (i >= n) return;
+    uint64_t mine[8];
+    load_name(names + kIndexSlot * i, v.name_bytes, mine);
+    owner[i] = lookup_name(v, mine);
+}
+
 __global__ __launch_bounds__(kIndexThreads) void rc_index_reinsert_kernel(IndexView v,
                                                                           const uint64_t *old_table,
                                                                           uint64_t old_entries) {
@@ -151,6 +165,13 @@ int rc_index_launch_resolve(const IndexView &v, const IndexWork &w, int64_t *own
     if (!w.slots) return 0;
     rc_index_resolve_kernel<<<groups_for(w.slots), kIndexThreads, 0, st>>>(v, w, owner, fresh);
     return index_status("rc_index_resolve_kernel");
+}
+
+int rc_index_launch_lookup(const IndexView &v, uint64_t n, const uint8_t *names, int64_t *owner,
+                           hipStream_t st) {
+    if (!n) return 0;
+    rc_index_lookup_kernel<<<groups_for(n), kIndexThreads, 0, st>>>(v, n, names, owner);
+    return index_status("rc_index_lookup_kernel");
 }
 
 int rc_index_launch_reinsert(const IndexView &v, const uint64_t *old_table, uint64_t old_entries,

@@ -27,6 +27,11 @@ struct IndexWork {
 
 const char *rc_index_launch_error(void);
 
+// An index's view for a launch of another module's (gc.hip's sweep reads the table and the pool).
+// The caller orders that launch against the index's other calls as it would order those.
+struct rc_index;
+int rc_index_view(rc_index *idx, IndexView *out);
+
 // pool[id_base + s] = the name at names + 64 s (the first name_bytes bytes), for the lanes of w.
 int rc_index_launch_stage(const IndexView &v, const IndexWork &w, const uint8_t *names, hipStream_t st);
 // Insert the pooled names of the lanes of w.
@@ -34,6 +39,10 @@ int rc_index_launch_insert(const IndexView &v, const IndexWork &w, hipStream_t s
 // owner[s], fresh[s] for the lanes of w (after the insert launch).
 int rc_index_launch_resolve(const IndexView &v, const IndexWork &w, int64_t *owner, uint8_t *fresh,
                             hipStream_t st);
+// owner[i] = the id the index holds for the name at names + 64 i (the first name_bytes bytes), -1
+// if none, -2 if the probe bound was exhausted; i < n.  Inserts nothing.
+int rc_index_launch_lookup(const IndexView &v, uint64_t n, const uint8_t *names, int64_t *owner,
+                           hipStream_t st);
 // Insert every id of old_table (old_entries of them) into v, whose pool already holds the names.
 int rc_index_launch_reinsert(const IndexView &v, const uint64_t *old_table, uint64_t old_entries,
                              hipStream_t st);
