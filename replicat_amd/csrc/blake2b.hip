@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "blake2b_lane.h"
+#include "capi_internal.h"
 #include "digest_kernels.h"
 
 namespace {
@@ -666,15 +667,6 @@ __global__ __launch_bounds__(256) void rc_b2_scatter_kernel(ChunkLists c,
 }
 
 namespace {
-thread_local char g_b2_err[256];
-
-int b2_status(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(g_b2_err, sizeof g_b2_err, "%s: %s", what, hipGetErrorString(e));
-    return 1;
-}
-
 unsigned b2_grid(uint64_t upper) {
     const uint64_t quads = kB2Threads / 4;
     uint64_t wg = (upper + quads - 1) / quads;
@@ -682,8 +674,6 @@ unsigned b2_grid(uint64_t upper) {
     return static_cast<unsigned>(wg ? wg : 1);
 }
 }  // namespace
-
-const char *rc_b2_launch_error(void) { return g_b2_err; }
 
 // lane-role workgroups for up to `upper` items: two waves per SIMD at most (kB2MaxGroups)
 static unsigned b2_lane_grid(uint64_t upper, uint64_t lane_max) {
@@ -706,12 +696,12 @@ int rc_b2_launch_items(const B2Item *d_items, uint64_t n, uint32_t outlen, uint8
     if (lane_only) {
         rc_b2_lane_kernel<<<b2_lane_only_grid(n), kB2Threads, 0, stream>>>(d_items, nullptr, n,
                                                                            outlen, d_out);
-        return b2_status("rc_b2_lane_kernel");
+        return rc::launch_status("rc_b2_lane_kernel");
     }
     const unsigned qg = b2_grid(n);
     rc_b2_kernel<<<qg + b2_lane_grid(n, lane_max), kB2Threads, 0, stream>>>(d_items, nullptr, n, outlen,
                                                                           d_out, lane_max, qg);
-    return b2_status("rc_b2_kernel");
+    return rc::launch_status("rc_b2_kernel");
 }
 
 int rc_b2_launch_sort(uint64_t n, const uint64_t *d_ptrs, const uint64_t *d_cut_base,
@@ -719,15 +709,15 @@ int rc_b2_launch_sort(uint64_t n, const uint64_t *d_ptrs, const uint64_t *d_cut_
                       uint32_t *d_hist, B2Item *d_items, hipStream_t stream) {
     if (!n) return 0;
     rc_b2_scan_kernel<<<1, 1024, 0, stream>>>(d_counts, n, d_chunk_off);
-    if (b2_status("rc_b2_scan_kernel")) return 1;
+    if (int rc = rc::launch_status("rc_b2_scan_kernel")) return rc;
     const ChunkLists c{d_ptrs, d_cut_base, d_cuts, d_counts, n, rc_b2_streams_per_group(n)};
     const unsigned groups = static_cast<unsigned>((n + c.spw - 1) / c.spw);
     rc_b2_hist_kernel<<<groups, 256, 0, stream>>>(c, d_hist);
-    if (b2_status("rc_b2_hist_kernel")) return 1;
+    if (int rc = rc::launch_status("rc_b2_hist_kernel")) return rc;
     rc_b2_hscan_kernel<<<1, 1024, 0, stream>>>(d_hist, uint64_t(kB2Buckets) * groups);
-    if (b2_status("rc_b2_hscan_kernel")) return 1;
+    if (int rc = rc::launch_status("rc_b2_hscan_kernel")) return rc;
     rc_b2_scatter_kernel<<<groups, 256, 0, stream>>>(c, d_hist, d_items);
-    return b2_status("rc_b2_scatter_kernel");
+    return rc::launch_status("rc_b2_scatter_kernel");
 }
 
 int rc_b2_launch_chunks(uint64_t n, const uint64_t *d_ptrs, const uint64_t *d_cut_base,
@@ -735,29 +725,29 @@ int rc_b2_launch_chunks(uint64_t n, const uint64_t *d_ptrs, const uint64_t *d_cu
                         uint32_t *d_hist, B2Item *d_items, uint64_t items_cap, uint32_t outlen,
                         uint8_t *d_out, uint64_t lane_max, bool lane_only, hipStream_t stream) {
     if (!n) return 0;
-    if (rc_b2_launch_sort(n, d_ptrs, d_cut_base, d_cuts, d_counts, d_chunk_off, d_hist, d_items, stream))
-        return 1;
+    if (int rc = rc_b2_launch_sort(n, d_ptrs, d_cut_base, d_cuts, d_counts, d_chunk_off, d_hist, d_items, stream))
+        return rc;
     if (lane_only) {
         rc_b2_lane_kernel<<<b2_lane_only_grid(items_cap), kB2Threads, 0, stream>>>(
             d_items, d_chunk_off + n, 0, outlen, d_out);
-        return b2_status("rc_b2_lane_kernel");
+        return rc::launch_status("rc_b2_lane_kernel");
     }
     const unsigned qg = b2_grid(items_cap);
     rc_b2_kernel<<<qg + b2_lane_grid(items_cap, lane_max), kB2Threads, 0, stream>>>(
         d_items, d_chunk_off + n, 0, outlen, d_out, lane_max, qg);
-    return b2_status("rc_b2_kernel");
+    return rc::launch_status("rc_b2_kernel");
 }
 
 int rc_b2_launch_update(const B2UItem *d_items, uint64_t n, uint8_t *d_out, hipStream_t stream) {
     if (!n) return 0;
     rc_b2_update_kernel<<<b2_grid(n), kB2Threads, 0, stream>>>(d_items, n, d_out);
-    return b2_status("rc_b2_update_kernel");
+    return rc::launch_status("rc_b2_update_kernel");
 }
 
 int rc_b2_launch_scan(const int64_t *d_counts, uint64_t n, uint64_t *d_chunk_off, hipStream_t stream) {
     if (!n) return 0;
     rc_b2_scan_kernel<<<1, 1024, 0, stream>>>(d_counts, n, d_chunk_off);
-    return b2_status("rc_b2_scan_kernel");
+    return rc::launch_status("rc_b2_scan_kernel");
 }
 
 int rc_b2_launch_derive(uint64_t n, const uint64_t *d_cut_base, const int64_t *d_counts,
@@ -769,5 +759,5 @@ int rc_b2_launch_derive(uint64_t n, const uint64_t *d_cut_base, const int64_t *d
     rc_b2_derive_kernel<<<groups, kB2Threads, 0, stream>>>(c, const_cast<rc_blake2b_state *>(d_kdf),
                                                            reinterpret_cast<uint64_t>(d_digests),
                                                            msg_len, d_keys);
-    return b2_status("rc_b2_derive_kernel");
+    return rc::launch_status("rc_b2_derive_kernel");
 }

@@ -29,26 +29,6 @@ namespace {
 
 thread_local char g_err[512];
 
-int vfail(int code, const char *fmt, va_list ap) {
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    return code;
-}
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vfail(code, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                  \
-    do {                                                                               \
-        const hipError_t e_ = (expr);                                                  \
-        if (e_ != hipSuccess)                                                          \
-            return fail(RC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));    \
-    } while (0)
-
 // Carry-less 64x64 -> 128 product.
 void clmul64(uint64_t a, uint64_t b, uint64_t &lo, uint64_t &hi) {
     lo = hi = 0;
@@ -98,7 +78,7 @@ uint64_t window_keys(uint64_t max_length) { return max_length >= 1 ? (max_length
 int rc_fail(int code, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
-    vfail(code, fmt, ap);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
     va_end(ap);
     return code;
 }
@@ -267,18 +247,18 @@ uint64_t cut_cap_of(uint64_t min_length, uint64_t L) {
 
 int validate_streams(uint64_t n, const uint8_t *const *ptrs, const uint64_t *lens,
                      const uint64_t *last, bool device_aligned) {
-    if (n && (!ptrs || !lens)) return fail(RC_ERR_ARGUMENT, "null stream arrays");
+    if (n && (!ptrs || !lens)) return rc_fail(RC_ERR_ARGUMENT, "null stream arrays");
     if (n >= (1ull << 31))  // tie markers carry the stream index in 31 bits (kernels.hip)
-        return fail(RC_ERR_ARGUMENT, "too many streams in one call: %llu", (unsigned long long)n);
+        return rc_fail(RC_ERR_ARGUMENT, "too many streams in one call: %llu", (unsigned long long)n);
     for (uint64_t i = 0; i < n; ++i) {
         const uint64_t P = last ? last[i] : 0;
-        if (P > lens[i]) return fail(RC_ERR_ARGUMENT, "stream %llu: last piece start %llu > length %llu",
-                                     (unsigned long long)i, (unsigned long long)P,
-                                     (unsigned long long)lens[i]);
-        if (lens[i] && !ptrs[i]) return fail(RC_ERR_ARGUMENT, "stream %llu: null pointer", (unsigned long long)i);
+        if (P > lens[i]) return rc_fail(RC_ERR_ARGUMENT, "stream %llu: last piece start %llu > length %llu",
+                                        (unsigned long long)i, (unsigned long long)P,
+                                        (unsigned long long)lens[i]);
+        if (lens[i] && !ptrs[i]) return rc_fail(RC_ERR_ARGUMENT, "stream %llu: null pointer", (unsigned long long)i);
         if (device_aligned && lens[i] && (reinterpret_cast<uintptr_t>(ptrs[i]) & 15))
-            return fail(RC_ERR_ALIGN, "stream %llu: device pointer not 16-byte aligned",
-                        (unsigned long long)i);
+            return rc_fail(RC_ERR_ALIGN, "stream %llu: device pointer not 16-byte aligned",
+                           (unsigned long long)i);
     }
     return 0;
 }
@@ -298,7 +278,7 @@ int stage_descriptors(rc_chunker *ch, Workspace &ws, uint64_t n, const uint8_t *
                       bool single = false, uint64_t walkers = 0) {
     plan.n = n;
     if (ws.pending) {  // the call that used this workspace before must be done with it
-        HIP_TRY(hipEventSynchronize(ws.done));
+        RC_HIP_TRY(hipEventSynchronize(ws.done));
         ws.pending = false;
     }
     // tiles the fast path does not take (kernels.hip tile_fast): a stream's tile 0 when the
@@ -383,7 +363,7 @@ int stage_descriptors(rc_chunker *ch, Workspace &ws, uint64_t n, const uint8_t *
     // tile indices are 32-bit in the tile kernel's units and tie lists (kernels.hip TileUnits):
     // 2^32 tiles = 64 TiB of stream per call
     if (tiles >= (1ull << 32) - (1ull << 20))
-        return fail(RC_ERR_ARGUMENT, "too many bytes in one call: %llu tiles", (unsigned long long)tiles);
+        return rc_fail(RC_ERR_ARGUMENT, "too many bytes in one call: %llu tiles", (unsigned long long)tiles);
     plan.n_tiles = tiles;
     plan.total_cap = cuts;
     plan.n_segs = segs;
@@ -424,7 +404,7 @@ int ensure_ctr(Workspace &ws, hipStream_t st) {
         zero = 256;
     }
     if (ws.ctr_dirty) {
-        HIP_TRY(hipMemsetAsync(ws.d_ctr.p, 0, zero, st));
+        RC_HIP_TRY(hipMemsetAsync(ws.d_ctr.p, 0, zero, st));
         ws.ctr_dirty = false;
     }
     return 0;
@@ -440,9 +420,9 @@ const char kFaultMsg[] =
 int grab_fault(Workspace &ws) {
     if (!ws.d_ctr.p || !ws.epoch) return 0;
     uint64_t stamp = 0;
-    HIP_TRY(hipMemcpy(&stamp, static_cast<uint32_t *>(ws.d_ctr.p) + kCtrStampWord, 8,
-                      hipMemcpyDeviceToHost));
-    return stamp == ws.epoch ? fail(RC_ERR_DEVICE_FAULT, "%s", kFaultMsg) : 0;
+    RC_HIP_TRY(hipMemcpy(&stamp, static_cast<uint32_t *>(ws.d_ctr.p) + kCtrStampWord, 8,
+                         hipMemcpyDeviceToHost));
+    return stamp == ws.epoch ? rc_fail(RC_ERR_DEVICE_FAULT, "%s", kFaultMsg) : 0;
 }
 
 // The faults the workspace's launches counted since the last call (rc_chunker_check), reset.
@@ -450,8 +430,8 @@ int take_faults(Workspace &ws, uint32_t &n) {
     n = 0;
     if (!ws.d_ctr.p) return 0;
     uint32_t *w = static_cast<uint32_t *>(ws.d_ctr.p) + kCtrFaultsWord;
-    HIP_TRY(hipMemcpy(&n, w, 4, hipMemcpyDeviceToHost));
-    if (n) HIP_TRY(hipMemset(w, 0, 4));
+    RC_HIP_TRY(hipMemcpy(&n, w, 4, hipMemcpyDeviceToHost));
+    if (n) RC_HIP_TRY(hipMemset(w, 0, 4));
     return 0;
 }
 
@@ -484,10 +464,10 @@ int upload_and_launch(rc_chunker *ch, Workspace &ws, const Plan &plan, ChainPara
     // last used this workspace, so its device buffer is free now, while the previous call's
     // kernels may still be running on `stream`.  `stream` waits for the upload only.
     const int wi = &ws == &ch->ws[0] ? 0 : 1;
-    if (!ch->cstream) HIP_TRY(hipStreamCreateWithFlags(&ch->cstream, hipStreamNonBlocking));
-    if (!ch->uploaded[wi]) HIP_TRY(hipEventCreateWithFlags(&ch->uploaded[wi], hipEventDisableTiming));
-    HIP_TRY(hipMemcpyAsync(ws.d_desc.p, ws.h_desc.p, plan.bytes, hipMemcpyHostToDevice, ch->cstream));
-    HIP_TRY(hipEventRecord(ch->uploaded[wi], ch->cstream));
+    if (!ch->cstream) RC_HIP_TRY(hipStreamCreateWithFlags(&ch->cstream, hipStreamNonBlocking));
+    if (!ch->uploaded[wi]) RC_HIP_TRY(hipEventCreateWithFlags(&ch->uploaded[wi], hipEventDisableTiming));
+    RC_HIP_TRY(hipMemcpyAsync(ws.d_desc.p, ws.h_desc.p, plan.bytes, hipMemcpyHostToDevice, ch->cstream));
+    RC_HIP_TRY(hipEventRecord(ch->uploaded[wi], ch->cstream));
     // ts: the tile kernel's stream, xs: the edge and chain kernels'.  A pipelined call's tile
     // kernel waits for what the caller queued on `stream` before the call (its inputs); the
     // caller's stream waits for nothing (rc_chunk_wait)
@@ -499,14 +479,14 @@ int upload_and_launch(rc_chunker *ch, Workspace &ws, const Plan &plan, ChainPara
         // the inputs: nothing to wait for when the caller's stream has no work pending (each
         // event record and wait is a packet between two tile kernels)
         if (hipStreamQuery(stream) != hipSuccess) {
-            HIP_TRY(hipEventRecord(ch->in_ev[wi], stream));
-            HIP_TRY(hipStreamWaitEvent(ts, ch->in_ev[wi], 0));
+            RC_HIP_TRY(hipEventRecord(ch->in_ev[wi], stream));
+            RC_HIP_TRY(hipStreamWaitEvent(ts, ch->in_ev[wi], 0));
         }
         // the chain kernels of consecutive calls stay in call order whichever stream they
         // are on (calls may share output arrays): wait for the previous call's
-        HIP_TRY(hipStreamWaitEvent(xs, ch->ws[wi ^ 1].done, 0));
+        RC_HIP_TRY(hipStreamWaitEvent(xs, ch->ws[wi ^ 1].done, 0));
     }
-    HIP_TRY(hipStreamWaitEvent(ts, ch->uploaded[wi], 0));
+    RC_HIP_TRY(hipStreamWaitEvent(ts, ch->uploaded[wi], 0));
     if (int rc = ensure_ctr(ws, ts)) return rc;
     // the call's epoch: its chain kernels compare it with the edge kernel's fault stamp
     prm.fault = reinterpret_cast<const uint64_t *>(static_cast<uint32_t *>(ws.d_ctr.p) + kCtrStampWord);
@@ -520,14 +500,14 @@ int upload_and_launch(rc_chunker *ch, Workspace &ws, const Plan &plan, ChainPara
         for (int k = 0; k < 4; ++k) {
             std::vector<hipEvent_t> &pool = k == 1 ? ch->ev_pool_sync : ch->ev_pool;
             if (pool.empty()) {
-                HIP_TRY(k == 1 ? hipEventCreate(&ev[k])
-                               : hipEventCreateWithFlags(&ev[k], hipEventDisableSystemFence));
+                RC_HIP_TRY(k == 1 ? hipEventCreate(&ev[k])
+                                  : hipEventCreateWithFlags(&ev[k], hipEventDisableSystemFence));
             } else {
                 ev[k] = pool.back();
                 pool.pop_back();
             }
         }
-        HIP_TRY(hipEventRecord(ev[0], ts));
+        RC_HIP_TRY(hipEventRecord(ev[0], ts));
     }
     GroupRecord *grp = ch->groups ? group_records(ws, plan) : nullptr;
     prm.grp = grp;
@@ -542,35 +522,35 @@ int upload_and_launch(rc_chunker *ch, Workspace &ws, const Plan &plan, ChainPara
     // 32-bit chain steps: small windows (the one-row record cache) and key indices < 2^32
     prm.lean = ch->small && plan.max_len < (16ull << 30) ? 1u : 0u;
     prm.hot = group_hot_threshold(ch->window);
-    if (rc_launch_tiles(ch->d_tables, d, plan.n, plan.n_tiles,
-                        static_cast<TileRecord *>(ws.d_records.p), grp, prm.hot, tie_lists(ws, plan),
-                        static_cast<uint32_t *>(ws.d_ctr.p), prm.epoch, ts,
-                        ch->timing ? ev[1] : nullptr,
-                        pipelined ? ch->tile_cus : 0u, xs,
-                        // the timing event after the tile kernel doubles as the hand-over event
-                        !pipelined ? nullptr : ch->timing ? ev[1] : ch->tiled[wi], ch->sched))
-        return abandon_launch(ws, ts, xs, fail(RC_ERR_HIP, "%s", rc_launch_error()));
+    if (int rc = rc_launch_tiles(ch->d_tables, d, plan.n, plan.n_tiles,
+                                 static_cast<TileRecord *>(ws.d_records.p), grp, prm.hot, tie_lists(ws, plan),
+                                 static_cast<uint32_t *>(ws.d_ctr.p), prm.epoch, ts,
+                                 ch->timing ? ev[1] : nullptr,
+                                 pipelined ? ch->tile_cus : 0u, xs,
+                                 // the timing event after the tile kernel doubles as the hand-over event
+                                 !pipelined ? nullptr : ch->timing ? ev[1] : ch->tiled[wi], ch->sched))
+        return abandon_launch(ws, ts, xs, rc);
     // A call in sequence after a pipelined one: that call's chain runs on another stream and
     // may still be writing cuts and counts that this call's chain writes too (calls may share
     // output arrays), so this chain waits for it.  (Pipelined calls wait above.)
     const Workspace &prev = ch->ws[wi ^ 1];
     if (!pipelined && prev.piped && hipStreamWaitEvent(xs, prev.done, 0) != hipSuccess)
-        return abandon_launch(ws, ts, xs, fail(RC_ERR_HIP, "hipStreamWaitEvent failed"));
+        return abandon_launch(ws, ts, xs, rc_fail(RC_ERR_HIP, "hipStreamWaitEvent failed"));
     if (ch->timing && hipEventRecord(ev[2], xs) != hipSuccess)
-        return abandon_launch(ws, ts, xs, fail(RC_ERR_HIP, "hipEventRecord failed"));
+        return abandon_launch(ws, ts, xs, rc_fail(RC_ERR_HIP, "hipEventRecord failed"));
     const uint32_t join = (ch->knobs[knJoinWalk] ? RC_JOIN_WALK_ONLY : 0u) |
                           (ch->knobs[knRepair] ? RC_JOIN_REPAIR : 0u);
-    if (rc_launch_chain(ch->d_tables, d, plan.n, prm, plan.n_segs,
-                        static_cast<const TileRecord *>(ws.d_records.p), d_cuts, d_counts,
-                        static_cast<uint64_t *>(ws.d_scratch.p),
-                        static_cast<uint64_t *>(ws.d_seg_counts.p), plan.any_multi, join, xs))
-        return abandon_launch(ws, ts, xs, fail(RC_ERR_HIP, "%s", rc_launch_error()));
+    if (int rc = rc_launch_chain(ch->d_tables, d, plan.n, prm, plan.n_segs,
+                                 static_cast<const TileRecord *>(ws.d_records.p), d_cuts, d_counts,
+                                 static_cast<uint64_t *>(ws.d_scratch.p),
+                                 static_cast<uint64_t *>(ws.d_seg_counts.p), plan.any_multi, join, xs))
+        return abandon_launch(ws, ts, xs, rc);
     if (hipEventRecord(ws.done, xs) != hipSuccess)
-        return abandon_launch(ws, ts, xs, fail(RC_ERR_HIP, "hipEventRecord failed"));
+        return abandon_launch(ws, ts, xs, rc_fail(RC_ERR_HIP, "hipEventRecord failed"));
     ws.pending = true;
     ws.piped = pipelined;
     if (ch->timing) {
-        HIP_TRY(hipEventRecord(ev[3], xs));
+        RC_HIP_TRY(hipEventRecord(ev[3], xs));
         ch->ev_rec.push_back(ev);
     }
     return 0;
@@ -591,17 +571,17 @@ int setup_overlap(rc_chunker *ch) {
     const uint32_t want = ch->reserve_req ? ch->reserve_req : (uint32_t)ch->knobs[knOverlapCus];
     if (ch->tstream && ch->reserve == want) return 0;
     int cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ch->device));
+    RC_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ch->device));
     if (want == 0 || (int)want >= cus)
-        return fail(RC_ERR_ARGUMENT, "overlap: %u reserved CUs of %d", want, cus);
+        return rc_fail(RC_ERR_ARGUMENT, "overlap: %u reserved CUs of %d", want, cus);
     if (ch->tstream) {  // a different split: retire the old pair
         if (ch->tstream2) {
-            HIP_TRY(hipStreamSynchronize(ch->tstream2));
+            RC_HIP_TRY(hipStreamSynchronize(ch->tstream2));
             (void)hipStreamDestroy(ch->tstream2);
             ch->tstream2 = nullptr;
         }
-        HIP_TRY(hipStreamSynchronize(ch->tstream));
-        HIP_TRY(hipStreamSynchronize(ch->xstream));
+        RC_HIP_TRY(hipStreamSynchronize(ch->tstream));
+        RC_HIP_TRY(hipStreamSynchronize(ch->xstream));
         (void)hipStreamDestroy(ch->tstream);
         (void)hipStreamDestroy(ch->xstream);
         ch->tstream = ch->xstream = nullptr;
@@ -615,14 +595,14 @@ int setup_overlap(rc_chunker *ch) {
     if (tmask == 1)
         for (int i = 0; i < cus; ++i) tm[i / 32] |= 1u << (i % 32);
     if (tmask == 2)
-        HIP_TRY(hipStreamCreateWithFlags(&ch->tstream, hipStreamNonBlocking));
+        RC_HIP_TRY(hipStreamCreateWithFlags(&ch->tstream, hipStreamNonBlocking));
     else
-        HIP_TRY(hipExtStreamCreateWithCUMask(&ch->tstream, (uint32_t)tm.size(), tm.data()));
+        RC_HIP_TRY(hipExtStreamCreateWithCUMask(&ch->tstream, (uint32_t)tm.size(), tm.data()));
     const hipError_t ex = hipExtStreamCreateWithCUMask(&ch->xstream, (uint32_t)xm.size(), xm.data());
     if (ex != hipSuccess) {  // both streams or neither (a call checks tstream only)
         (void)hipStreamDestroy(ch->tstream);
         ch->tstream = ch->xstream = nullptr;
-        return fail(RC_ERR_HIP, "hipExtStreamCreateWithCUMask failed: %s", hipGetErrorString(ex));
+        return rc_fail(RC_ERR_HIP, "hipExtStreamCreateWithCUMask failed: %s", hipGetErrorString(ex));
     }
     // RC_TILE_STREAMS=2: odd calls' tile kernels on a second stream with the same mask (a queue
     // of its own), so that a call's tile kernel is not held behind the previous one's last
@@ -633,10 +613,10 @@ int setup_overlap(rc_chunker *ch) {
                     : hipExtStreamCreateWithCUMask(&ch->tstream2, (uint32_t)tm.size(), tm.data())) !=
             hipSuccess)
         ch->tstream2 = nullptr;  // one tile stream: still correct
-    if (!ch->fstream) HIP_TRY(hipStreamCreateWithFlags(&ch->fstream, hipStreamNonBlocking));
+    if (!ch->fstream) RC_HIP_TRY(hipStreamCreateWithFlags(&ch->fstream, hipStreamNonBlocking));
     for (int i = 0; i < 2; ++i) {
-        if (!ch->in_ev[i]) HIP_TRY(hipEventCreateWithFlags(&ch->in_ev[i], hipEventDisableTiming));
-        if (!ch->tiled[i]) HIP_TRY(hipEventCreateWithFlags(&ch->tiled[i], hipEventDisableTiming));
+        if (!ch->in_ev[i]) RC_HIP_TRY(hipEventCreateWithFlags(&ch->in_ev[i], hipEventDisableTiming));
+        if (!ch->tiled[i]) RC_HIP_TRY(hipEventCreateWithFlags(&ch->tiled[i], hipEventDisableTiming));
     }
     ch->reserve = want;
     ch->tile_cus = (uint32_t)cus - (tmask ? 0u : want);
@@ -705,26 +685,26 @@ uint64_t rc_keys_needed(uint64_t max_length, uint64_t L, uint64_t P) {
 
 int rc_chunker_create(uint64_t min_length, uint64_t max_length, const uint8_t *key,
                       uint64_t key_len, int device, rc_chunker **out) {
-    if (!out) return fail(RC_ERR_ARGUMENT, "null output handle");
+    if (!out) return rc_fail(RC_ERR_ARGUMENT, "null output handle");
     *out = nullptr;
     // adapters.cpp:21-29, in the reference's order
-    if (key_len != 16 || !key) return fail(RC_ERR_KEY_LENGTH, "key must contain exactly 16 characters");
+    if (key_len != 16 || !key) return rc_fail(RC_ERR_KEY_LENGTH, "key must contain exactly 16 characters");
     if (min_length > max_length)
-        return fail(RC_ERR_MIN_GT_MAX, "Minimum length is greater than the maximum one");
+        return rc_fail(RC_ERR_MIN_GT_MAX, "Minimum length is greater than the maximum one");
     const uint64_t k0 = load_le64(key), k1 = load_le64(key + 8);
-    if (k0 == 0) return fail(RC_ERR_BAD_KEY, "Bad key contents");
+    if (k0 == 0) return rc_fail(RC_ERR_BAD_KEY, "Bad key contents");
     // the environment knobs (knobs.h), once: a malformed one is an error, not a silent default
     Knobs knobs;
     if (read_knobs(knobs, g_err, sizeof g_err)) return RC_ERR_ARGUMENT;
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RC_ERR_NO_DEVICE, "no HIP device available (the chunker runs on MI355X only)");
-    if (device < 0 || device >= ndev) return fail(RC_ERR_NO_DEVICE, "device %d out of range", device);
+        return rc_fail(RC_ERR_NO_DEVICE, "no HIP device available (the chunker runs on MI355X only)");
+    if (device < 0 || device >= ndev) return rc_fail(RC_ERR_NO_DEVICE, "device %d out of range", device);
     hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    RC_HIP_TRY(hipGetDeviceProperties(&prop, device));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(RC_ERR_NO_DEVICE, "device %d is %s, not gfx950", device, prop.gcnArchName);
+        return rc_fail(RC_ERR_NO_DEVICE, "device %d is %s, not gfx950", device, prop.gcnArchName);
 
     rc_chunker *ch = new rc_chunker();
     ch->min_length = min_length;
@@ -766,7 +746,7 @@ int rc_chunker_create(uint64_t min_length, uint64_t max_length, const uint8_t *k
             if (e == hipSuccess) e = hipEventCreateWithFlags(&w.done, hipEventDisableTiming);
         if (e != hipSuccess) {
             rc_chunker_destroy(ch);
-            return fail(RC_ERR_HIP, "device setup failed: %s", hipGetErrorString(e));
+            return rc_fail(RC_ERR_HIP, "device setup failed: %s", hipGetErrorString(e));
         }
     }
     rc_track(ch, [](void *h) { rc_chunker_destroy(static_cast<rc_chunker *>(h)); });
@@ -776,13 +756,7 @@ int rc_chunker_create(uint64_t min_length, uint64_t max_length, const uint8_t *k
 
 void rc_chunker_destroy(rc_chunker *ch) {
     if (!ch) return;
-    rc_untrack(ch);
-    {
-        // a call still running on another thread (a daemon thread when the exit hook runs)
-        // finishes first: its buffers and streams go only after it
-        std::lock_guard<std::mutex> lock(ch->mu);
-        DeviceGuard g(ch->device);
-        (void)hipDeviceSynchronize();
+    teardown(ch, [ch] {
         if (ch->d_tables) (void)hipFree(ch->d_tables);
         for (auto &w : ch->ws) {
             w.d_desc.release();
@@ -818,7 +792,7 @@ void rc_chunker_destroy(rc_chunker *ch) {
             for (auto e : r) (void)hipEventDestroy(e);
         for (auto e : ch->ev_pool) (void)hipEventDestroy(e);
         for (auto e : ch->ev_pool_sync) (void)hipEventDestroy(e);
-    }
+    });
     delete ch;
 }
 
@@ -834,7 +808,7 @@ uint64_t rc_host_key(const rc_chunker *ch, uint64_t d) {
 
 int rc_tables_key(const uint8_t *key16, uint64_t n, const uint64_t *ds, uint64_t *out,
                   uint32_t *top16) {
-    if (!key16 || (n && (!ds || !out))) return fail(RC_ERR_ARGUMENT, "null argument");
+    if (!key16 || (n && (!ds || !out))) return rc_fail(RC_ERR_ARGUMENT, "null argument");
     KeyTables *t = new KeyTables;
     build_tables(load_le64(key16), load_le64(key16 + 8), *t);
     for (uint64_t i = 0; i < n; ++i) {
@@ -865,8 +839,8 @@ uint64_t rc_cut_capacity(const rc_chunker *ch, uint64_t n, const uint64_t *lens,
 }
 
 int rc_next_cut(rc_chunker *ch, const uint8_t *buffer, uint64_t size, int final, uint64_t *out_cut) {
-    if (!ch || !out_cut) return fail(RC_ERR_ARGUMENT, "null argument");
-    if (size && !buffer) return fail(RC_ERR_ARGUMENT, "null buffer");
+    if (!ch || !out_cut) return rc_fail(RC_ERR_ARGUMENT, "null argument");
+    if (size && !buffer) return rc_fail(RC_ERR_ARGUMENT, "null buffer");
     const uint64_t mn = ch->min_length, mx = ch->max_length;
     // adapters.cpp:48-57
     if (final && size < 2 * mx) {
@@ -889,7 +863,7 @@ int rc_next_cut(rc_chunker *ch, const uint8_t *buffer, uint64_t size, int final,
     if (int rc = ch->d_out.ensure(64)) return rc;
     if (int rc = ch->h_out.ensure(64)) return rc;
     hipStream_t stream = nullptr;
-    HIP_TRY(hipMemcpyAsync(ch->d_buf.p, buffer, ncopy, hipMemcpyHostToDevice, stream));
+    RC_HIP_TRY(hipMemcpyAsync(ch->d_buf.p, buffer, ncopy, hipMemcpyHostToDevice, stream));
     const uint8_t *ptr = static_cast<const uint8_t *>(ch->d_buf.p);
     const uint64_t L = ncopy, P = ncopy;
     Plan plan;
@@ -902,11 +876,11 @@ int rc_next_cut(rc_chunker *ch, const uint8_t *buffer, uint64_t size, int final,
     int rc = upload_and_launch(ch, ws, plan, chain_params(ch, plan, 0), d_cut, d_count, stream);
     ch->timing = timing;
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(ch->h_out.p, d_cut, 16, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    RC_HIP_TRY(hipMemcpyAsync(ch->h_out.p, d_cut, 16, hipMemcpyDeviceToHost, stream));
+    RC_HIP_TRY(hipStreamSynchronize(stream));
     const uint64_t *h = static_cast<const uint64_t *>(ch->h_out.p);
-    if ((int64_t)h[1] == kCountFault) return fail(RC_ERR_DEVICE_FAULT, "%s", kFaultMsg);
-    if ((int64_t)h[1] != 1) return fail(RC_ERR_OVERFLOW, "device chain returned %lld cuts", (long long)h[1]);
+    if ((int64_t)h[1] == kCountFault) return rc_fail(RC_ERR_DEVICE_FAULT, "%s", kFaultMsg);
+    if ((int64_t)h[1] != 1) return rc_fail(RC_ERR_OVERFLOW, "device chain returned %lld cuts", (long long)h[1]);
     *out_cut = h[0];
     return RC_OK;
 }
@@ -914,9 +888,9 @@ int rc_next_cut(rc_chunker *ch, const uint8_t *buffer, uint64_t size, int final,
 int rc_chunk_device(rc_chunker *ch, uint64_t n, const uint8_t *const *d_streams,
                     const uint64_t *lens, const uint64_t *last_piece, uint32_t flags,
                     uint64_t *d_cuts, int64_t *d_counts, void *hip_stream) {
-    if (!ch) return fail(RC_ERR_ARGUMENT, "null chunker");
+    if (!ch) return rc_fail(RC_ERR_ARGUMENT, "null chunker");
     if (n == 0) return RC_OK;
-    if (!d_cuts || !d_counts) return fail(RC_ERR_ARGUMENT, "null output arrays");
+    if (!d_cuts || !d_counts) return rc_fail(RC_ERR_ARGUMENT, "null output arrays");
     const bool open = (flags & RC_OPEN) != 0;
     if (int rc = validate_streams(n, d_streams, lens, open ? nullptr : last_piece, true)) return rc;
     // Small-window chunkers (group records, lane / quad chains: config 3 iii) run a pipelined
@@ -964,18 +938,16 @@ int rc_chunk_device(rc_chunker *ch, uint64_t n, const uint8_t *const *d_streams,
 }
 
 int rc_stream_create(int device, void **out_stream) {
-    if (!out_stream) return fail(RC_ERR_ARGUMENT, "null output stream");
+    if (!out_stream) return rc_fail(RC_ERR_ARGUMENT, "null output stream");
     *out_stream = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return fail(RC_ERR_NO_DEVICE, "no HIP device %d", device);
+    if (int rc = check_device(device)) return rc;
     DeviceGuard g(device);
     int cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    RC_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
     std::vector<uint32_t> mask((cus + 31) / 32, 0u);
     for (int i = 0; i < cus; ++i) mask[i / 32] |= 1u << (i % 32);
     hipStream_t s = nullptr;
-    HIP_TRY(hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data()));
+    RC_HIP_TRY(hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data()));
     rc_track(s, [](void *h) { rc_stream_destroy(h); });
     *out_stream = s;
     return RC_OK;
@@ -989,7 +961,7 @@ void rc_stream_destroy(void *stream) {
 }
 
 int rc_chunker_overlap(rc_chunker *ch, uint32_t reserve_cus) {
-    if (!ch) return fail(RC_ERR_ARGUMENT, "null chunker");
+    if (!ch) return rc_fail(RC_ERR_ARGUMENT, "null chunker");
     std::lock_guard<std::mutex> lock(ch->mu);
     DeviceGuard g(ch->device);
     ch->reserve_req = reserve_cus;
@@ -1003,29 +975,29 @@ uint32_t rc_chunker_overlap_cus(const rc_chunker *ch) { return ch ? ch->reserve 
 uint64_t rc_chunker_pipelined_calls(const rc_chunker *ch) { return ch ? ch->pipelined_calls : 0; }
 
 int rc_chunker_check(rc_chunker *ch) {
-    if (!ch) return fail(RC_ERR_ARGUMENT, "null chunker");
+    if (!ch) return rc_fail(RC_ERR_ARGUMENT, "null chunker");
     std::lock_guard<std::mutex> lock(ch->mu);
     DeviceGuard g(ch->device);
     uint32_t faults = 0;
     for (auto &w : ch->ws) {
-        if (w.pending) HIP_TRY(hipEventSynchronize(w.done));
+        if (w.pending) RC_HIP_TRY(hipEventSynchronize(w.done));
         uint32_t n = 0;
         if (int rc = take_faults(w, n)) return rc;
         faults += n;
     }
     if (faults)
-        return fail(RC_ERR_DEVICE_FAULT, "%s (%u call(s) since the last check)", kFaultMsg, faults);
+        return rc_fail(RC_ERR_DEVICE_FAULT, "%s (%u call(s) since the last check)", kFaultMsg, faults);
     return RC_OK;
 }
 
 int rc_chunk_wait(rc_chunker *ch, void *hip_stream) {
-    if (!ch) return fail(RC_ERR_ARGUMENT, "null chunker");
+    if (!ch) return rc_fail(RC_ERR_ARGUMENT, "null chunker");
     std::lock_guard<std::mutex> lock(ch->mu);
     DeviceGuard g(ch->device);
     // a workspace's `done` was recorded by its last call, after the host had waited for the
     // call before that one on the same workspace: the two events cover every call so far
     for (auto &w : ch->ws)
-        HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), w.done, 0));
+        RC_HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), w.done, 0));
     return RC_OK;
 }
 
@@ -1038,16 +1010,16 @@ namespace {
 int chunk_host_impl(rc_chunker *ch, rc_hasher *hasher, uint64_t n, const uint8_t *const *streams,
                     const uint64_t *lens, const uint64_t *last_piece, uint32_t flags,
                     uint64_t *cuts, int64_t *counts, uint8_t *digests) {
-    if (!ch) return fail(RC_ERR_ARGUMENT, "null chunker");
+    if (!ch) return rc_fail(RC_ERR_ARGUMENT, "null chunker");
     if (n == 0) return RC_OK;
-    if (!cuts || !counts) return fail(RC_ERR_ARGUMENT, "null output arrays");
-    if (hasher && !digests) return fail(RC_ERR_ARGUMENT, "null digest array");
+    if (!cuts || !counts) return rc_fail(RC_ERR_ARGUMENT, "null output arrays");
+    if (hasher && !digests) return rc_fail(RC_ERR_ARGUMENT, "null digest array");
     const bool open = (flags & RC_OPEN) != 0;
     if (int rc = validate_streams(n, streams, lens, open ? nullptr : last_piece, false)) return rc;
     std::lock_guard<std::mutex> lock(ch->mu);
     DeviceGuard g(ch->device);
     for (int i = 0; i < 2; ++i)
-        if (!ch->hstream[i]) HIP_TRY(hipStreamCreateWithFlags(&ch->hstream[i], hipStreamNonBlocking));
+        if (!ch->hstream[i]) RC_HIP_TRY(hipStreamCreateWithFlags(&ch->hstream[i], hipStreamNonBlocking));
     // an error return leaves no copy into the caller's arrays pending: whatever either slot
     // has enqueued is waited for first (the error already recorded is the one reported)
     struct Drain {
@@ -1074,14 +1046,14 @@ int chunk_host_impl(rc_chunker *ch, rc_hasher *hasher, uint64_t n, const uint8_t
 
     auto finish = [&](int slot) -> int {
         if (!busy[slot]) return 0;
-        HIP_TRY(hipStreamSynchronize(ch->hstream[slot]));
+        RC_HIP_TRY(hipStreamSynchronize(ch->hstream[slot]));
         busy[slot] = false;
         const Batch &b = inflight[slot];
         for (uint64_t i = 0; i < b.count; ++i) {
-            if (counts[b.first + i] == kCountFault) return fail(RC_ERR_DEVICE_FAULT, "%s", kFaultMsg);
+            if (counts[b.first + i] == kCountFault) return rc_fail(RC_ERR_DEVICE_FAULT, "%s", kFaultMsg);
             if (counts[b.first + i] < 0)
-                return fail(RC_ERR_OVERFLOW, "stream %llu overflowed its cut capacity",
-                            (unsigned long long)(b.first + i));
+                return rc_fail(RC_ERR_OVERFLOW, "stream %llu overflowed its cut capacity",
+                               (unsigned long long)(b.first + i));
         }
         return 0;
     };
@@ -1106,7 +1078,7 @@ int chunk_host_impl(rc_chunker *ch, rc_hasher *hasher, uint64_t n, const uint8_t
         for (uint64_t k = 0; k < nb; ++k) {
             uint8_t *dst = static_cast<uint8_t *>(ch->d_stage[slot].p) + o;
             dptr[k] = dst;
-            if (lens[i + k]) HIP_TRY(hipMemcpyAsync(dst, streams[i + k], lens[i + k], hipMemcpyHostToDevice, st));
+            if (lens[i + k]) RC_HIP_TRY(hipMemcpyAsync(dst, streams[i + k], lens[i + k], hipMemcpyHostToDevice, st));
             o += (lens[i + k] + 15) & ~15ull;
         }
         Plan plan;
@@ -1131,11 +1103,11 @@ int chunk_host_impl(rc_chunker *ch, rc_hasher *hasher, uint64_t n, const uint8_t
             if (int rc = rc_hasher_enqueue_chunks(hasher, nb, dptr.data(), cb.data(), dc, dn, ncut,
                                                   bytes, std::min(longest, ch->max_length), dd, st))
                 return rc;
-            HIP_TRY(hipMemcpyAsync(digests + cut_base[i] * kDigestSlot, dd, ncut * kDigestSlot,
-                                   hipMemcpyDeviceToHost, st));
+            RC_HIP_TRY(hipMemcpyAsync(digests + cut_base[i] * kDigestSlot, dd, ncut * kDigestSlot,
+                                      hipMemcpyDeviceToHost, st));
         }
-        HIP_TRY(hipMemcpyAsync(cuts + cut_base[i], dc, ncut * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(counts + i, dn, nb * 8, hipMemcpyDeviceToHost, st));
+        RC_HIP_TRY(hipMemcpyAsync(cuts + cut_base[i], dc, ncut * 8, hipMemcpyDeviceToHost, st));
+        RC_HIP_TRY(hipMemcpyAsync(counts + i, dn, nb * 8, hipMemcpyDeviceToHost, st));
         inflight[slot] = {i, nb};
         busy[slot] = true;
         i = j;
@@ -1159,7 +1131,7 @@ int rc_chunk_host(rc_chunker *ch, uint64_t n, const uint8_t *const *streams, con
 int rc_chunk_digest_host(rc_chunker *ch, rc_hasher *h, uint64_t n, const uint8_t *const *streams,
                          const uint64_t *lens, const uint64_t *last_piece, uint32_t flags,
                          uint64_t *cuts, int64_t *counts, uint8_t *digests) {
-    if (!h) return fail(RC_ERR_ARGUMENT, "null hasher");
+    if (!h) return rc_fail(RC_ERR_ARGUMENT, "null hasher");
     return chunk_host_impl(ch, h, n, streams, lens, last_piece, flags, cuts, counts, digests);
 }
 
@@ -1169,7 +1141,7 @@ int rc_tile_records(rc_chunker *ch, uint64_t n, const uint8_t *const *d_streams,
                     const uint64_t *lens, const uint64_t *last_piece, uint64_t *keys,
                     uint64_t *js, uint64_t *gmax, uint64_t *ghot, uint64_t cap,
                     uint64_t *n_tiles) {
-    if (!ch || !n_tiles) return fail(RC_ERR_ARGUMENT, "null argument");
+    if (!ch || !n_tiles) return rc_fail(RC_ERR_ARGUMENT, "null argument");
     if (int rc = validate_streams(n, d_streams, lens, last_piece, true)) return rc;
     std::lock_guard<std::mutex> lock(ch->mu);
     DeviceGuard g(ch->device);
@@ -1178,27 +1150,27 @@ int rc_tile_records(rc_chunker *ch, uint64_t n, const uint8_t *const *d_streams,
     if (int rc = stage_descriptors(ch, ws, n, d_streams, lens, last_piece, plan)) return rc;
     if (int rc = ws.d_desc.ensure(plan.bytes)) return rc;
     if (int rc = ws.d_records.ensure(records_bytes(plan))) return rc;
-    HIP_TRY(hipMemcpy(ws.d_desc.p, ws.h_desc.p, plan.bytes, hipMemcpyHostToDevice));
+    RC_HIP_TRY(hipMemcpy(ws.d_desc.p, ws.h_desc.p, plan.bytes, hipMemcpyHostToDevice));
     if (int rc = ensure_ctr(ws, nullptr)) return rc;
     GroupRecord *d_grp = ch->groups ? group_records(ws, plan) : nullptr;
     // poison the records first: a tile the schedule never ran shows as 0xabab.. keys
     if (plan.n_tiles)
-        HIP_TRY(hipMemset(ws.d_records.p, 0xab, (plan.n_tiles + 1) * sizeof(TileRecord)));
-    if (rc_launch_tiles(ch->d_tables, desc_view(ws.d_desc.p, n), n, plan.n_tiles,
-                        static_cast<TileRecord *>(ws.d_records.p), d_grp,
-                        group_hot_threshold(ch->window), tie_lists(ws, plan),
-                        static_cast<uint32_t *>(ws.d_ctr.p), ++ws.epoch, nullptr, nullptr, 0u,
-                        nullptr, nullptr, ch->sched))
-        return abandon_launch(ws, nullptr, nullptr, fail(RC_ERR_HIP, "%s", rc_launch_error()));
-    HIP_TRY(hipDeviceSynchronize());
+        RC_HIP_TRY(hipMemset(ws.d_records.p, 0xab, (plan.n_tiles + 1) * sizeof(TileRecord)));
+    if (int rc = rc_launch_tiles(ch->d_tables, desc_view(ws.d_desc.p, n), n, plan.n_tiles,
+                                 static_cast<TileRecord *>(ws.d_records.p), d_grp,
+                                 group_hot_threshold(ch->window), tie_lists(ws, plan),
+                                 static_cast<uint32_t *>(ws.d_ctr.p), ++ws.epoch, nullptr, nullptr, 0u,
+                                 nullptr, nullptr, ch->sched))
+        return abandon_launch(ws, nullptr, nullptr, rc);
+    RC_HIP_TRY(hipDeviceSynchronize());
     if (int rc = grab_fault(ws)) return rc;
     std::vector<TileRecord> h(plan.n_tiles);
     std::vector<GroupRecord> hg(plan.n_tiles, GroupRecord{~0ull, {~0ull, ~0ull, ~0ull, ~0ull}, 0ull});
     if (plan.n_tiles) {
-        HIP_TRY(hipMemcpy(h.data(), ws.d_records.p, plan.n_tiles * sizeof(TileRecord),
-                          hipMemcpyDeviceToHost));
+        RC_HIP_TRY(hipMemcpy(h.data(), ws.d_records.p, plan.n_tiles * sizeof(TileRecord),
+                             hipMemcpyDeviceToHost));
         if (d_grp)
-            HIP_TRY(hipMemcpy(hg.data(), d_grp, plan.n_tiles * sizeof(GroupRecord), hipMemcpyDeviceToHost));
+            RC_HIP_TRY(hipMemcpy(hg.data(), d_grp, plan.n_tiles * sizeof(GroupRecord), hipMemcpyDeviceToHost));
     }
     *n_tiles = plan.n_tiles;
     for (uint64_t t = 0; t < plan.n_tiles && t < cap; ++t) {
@@ -1212,22 +1184,22 @@ int rc_tile_records(rc_chunker *ch, uint64_t n, const uint8_t *const *d_streams,
 }
 
 int rc_timing_enable(rc_chunker *ch, int enable) {
-    if (!ch) return fail(RC_ERR_ARGUMENT, "null chunker");
+    if (!ch) return rc_fail(RC_ERR_ARGUMENT, "null chunker");
     ch->timing = enable != 0;
     return RC_OK;
 }
 
 int rc_timing_read_kernels(rc_chunker *ch, double *tile_ms, double *edge_ms, double *chain_ms,
                            uint64_t *calls) {
-    if (!ch) return fail(RC_ERR_ARGUMENT, "null chunker");
+    if (!ch) return rc_fail(RC_ERR_ARGUMENT, "null chunker");
     std::lock_guard<std::mutex> lock(ch->mu);
     DeviceGuard g(ch->device);
     double t[3] = {0, 0, 0};
     for (auto &r : ch->ev_rec) {
-        HIP_TRY(hipEventSynchronize(r[3]));
+        RC_HIP_TRY(hipEventSynchronize(r[3]));
         for (int k = 0; k < 3; ++k) {
             float x = 0;
-            HIP_TRY(hipEventElapsedTime(&x, r[k], r[k + 1]));
+            RC_HIP_TRY(hipEventElapsedTime(&x, r[k], r[k + 1]));
             t[k] += x;
         }
         for (int k = 0; k < 4; ++k) (k == 1 ? ch->ev_pool_sync : ch->ev_pool).push_back(r[k]);
@@ -1249,8 +1221,8 @@ int rc_timing_read(rc_chunker *ch, double *phase_a_ms, double *phase_b_ms, uint6
 }
 
 int rc_read_probe(const uint8_t *d_src, uint64_t nbytes, uint32_t *d_out, void *hip_stream) {
-    if (nbytes && (!d_src || !d_out)) return fail(RC_ERR_ARGUMENT, "null argument");
-    if (reinterpret_cast<uintptr_t>(d_src) & 15) return fail(RC_ERR_ALIGN, "source not 16-byte aligned");
+    if (nbytes && (!d_src || !d_out)) return rc_fail(RC_ERR_ARGUMENT, "null argument");
+    if (reinterpret_cast<uintptr_t>(d_src) & 15) return rc_fail(RC_ERR_ALIGN, "source not 16-byte aligned");
     // the tile kernel's schedule as a chunker created now would run it (the process's knobs)
     const Knobs &k = process_knobs();
     TileSched sched;
@@ -1258,46 +1230,38 @@ int rc_read_probe(const uint8_t *d_src, uint64_t nbytes, uint32_t *d_out, void *
     sched.chunk = (uint32_t)k[knTileChunk];
     sched.dyn_min = (uint32_t)k[knTileDynMin];
     sched.group = (uint32_t)k[knTileGroup];
-    if (rc_launch_read_probe(d_src, nbytes, d_out, (uint32_t)k[knProbeBlock], sched, hip_stream))
-        return fail(RC_ERR_HIP, "%s", rc_launch_error());
-    return RC_OK;
+    return rc_launch_read_probe(d_src, nbytes, d_out, (uint32_t)k[knProbeBlock], sched, hip_stream);
 }
 
 int rc_chunker_read_probe(rc_chunker *ch, const uint8_t *d_src, uint64_t nbytes, uint32_t *d_out,
                           void *hip_stream) {
-    if (!ch) return fail(RC_ERR_ARGUMENT, "null chunker");
-    if (nbytes && (!d_src || !d_out)) return fail(RC_ERR_ARGUMENT, "null argument");
-    if (reinterpret_cast<uintptr_t>(d_src) & 15) return fail(RC_ERR_ALIGN, "source not 16-byte aligned");
+    if (!ch) return rc_fail(RC_ERR_ARGUMENT, "null chunker");
+    if (nbytes && (!d_src || !d_out)) return rc_fail(RC_ERR_ARGUMENT, "null argument");
+    if (reinterpret_cast<uintptr_t>(d_src) & 15) return rc_fail(RC_ERR_ALIGN, "source not 16-byte aligned");
     DeviceGuard g(ch->device);
-    if (rc_launch_read_probe(d_src, nbytes, d_out, 0, ch->sched, hip_stream))
-        return fail(RC_ERR_HIP, "%s", rc_launch_error());
-    return RC_OK;
+    return rc_launch_read_probe(d_src, nbytes, d_out, 0, ch->sched, hip_stream);
 }
 
 int rc_fill_splitmix(uint8_t *d_dst, uint64_t nbytes, uint64_t seed, uint64_t stream, void *hip_stream) {
-    if (nbytes && !d_dst) return fail(RC_ERR_ARGUMENT, "null destination");
-    if (rc_launch_fill(d_dst, nbytes, seed, stream, 0, hip_stream)) return fail(RC_ERR_HIP, "%s", rc_launch_error());
-    return RC_OK;
+    if (nbytes && !d_dst) return rc_fail(RC_ERR_ARGUMENT, "null destination");
+    return rc_launch_fill(d_dst, nbytes, seed, stream, 0, hip_stream);
 }
 
 int rc_fill_splitmix_streams(uint8_t *d_dst, uint64_t n, uint64_t nbytes, uint64_t slot,
                              uint64_t seed, uint64_t first_stream, uint64_t stream_step,
                              void *hip_stream) {
-    if (n && nbytes && !d_dst) return fail(RC_ERR_ARGUMENT, "null destination");
+    if (n && nbytes && !d_dst) return rc_fail(RC_ERR_ARGUMENT, "null destination");
     if (slot % 8 || slot < ((nbytes + 7) & ~7ull))
-        return fail(RC_ERR_ARGUMENT, "slot %llu must be a multiple of 8 holding %llu bytes",
-                    (unsigned long long)slot, (unsigned long long)nbytes);
-    if (reinterpret_cast<uintptr_t>(d_dst) & 7) return fail(RC_ERR_ALIGN, "destination not 8-byte aligned");
-    if (rc_launch_fill_streams(d_dst, n, nbytes, slot, seed, first_stream, stream_step, hip_stream))
-        return fail(RC_ERR_HIP, "%s", rc_launch_error());
-    return RC_OK;
+        return rc_fail(RC_ERR_ARGUMENT, "slot %llu must be a multiple of 8 holding %llu bytes",
+                       (unsigned long long)slot, (unsigned long long)nbytes);
+    if (reinterpret_cast<uintptr_t>(d_dst) & 7) return rc_fail(RC_ERR_ALIGN, "destination not 8-byte aligned");
+    return rc_launch_fill_streams(d_dst, n, nbytes, slot, seed, first_stream, stream_step, hip_stream);
 }
 
 int rc_fill_splitmix_at(uint8_t *d_dst, uint64_t nbytes, uint64_t seed, uint64_t stream,
                         uint64_t word0, void *hip_stream) {
-    if (nbytes && !d_dst) return fail(RC_ERR_ARGUMENT, "null destination");
-    if (rc_launch_fill(d_dst, nbytes, seed, stream, word0, hip_stream)) return fail(RC_ERR_HIP, "%s", rc_launch_error());
-    return RC_OK;
+    if (nbytes && !d_dst) return rc_fail(RC_ERR_ARGUMENT, "null destination");
+    return rc_launch_fill(d_dst, nbytes, seed, stream, word0, hip_stream);
 }
 
 }  // extern "C"

@@ -32,8 +32,7 @@ int launch(const CipherCore *, int mode, const GcmItem *items, const uint64_t *d
     a.n = n;
     a.ok = ok;
     GCM_DBG("chacha launch mode=%d n=%llu", mode, (unsigned long long)n);
-    if (rc_chacha_launch(mode, a, st)) return rc_fail(RC_ERR_HIP, "%s", rc_chacha_launch_error());
-    return 0;
+    return rc_chacha_launch(mode, a, st);
 }
 
 // 32-byte keys and 12-byte nonces, in 32- and 16-byte slots of the host image

@@ -104,9 +104,7 @@ int launch(const CipherCore *core, int mode, const GcmItem *items, const uint64_
     const unsigned groups = static_cast<unsigned>(std::max<uint64_t>(n, 1));
     GCM_DBG("launch %s n=%llu groups=%u", mode == kDecrypt ? "decrypt" : "encrypt", (unsigned long long)n,
             groups);
-    if (rc_gcm_launch(g->desc.key_bytes, mode == kDecrypt, a, groups, st))
-        return rc_fail(RC_ERR_HIP, "%s", rc_gcm_launch_error());
-    return 0;
+    return rc_gcm_launch(g->desc.key_bytes, mode == kDecrypt, a, groups, st);
 }
 
 // core_create's setup: the constant tables

@@ -29,16 +29,14 @@ struct rc_hasher {
     int device = 0;
     rc::Knobs knobs;  // knobs.h, read once at creation (the lane / quad split)
     std::mutex mu;
-    struct Workspace {
+    struct Staging {
         rc::PinnedBuf h_stage;   // host-built descriptors / items
         rc::DevBuf d_stage;      // their device copy
         rc::DevBuf d_items;      // work list of the chunk path
         rc::DevBuf d_tags;       // SHA updates: the states' algorithm words ..
         rc::PinnedBuf h_tags;    // .. and their host copy
-        hipEvent_t done = nullptr;
-        bool pending = false;
-    } ws[2];
-    unsigned next_ws = 0;
+    };
+    rc::SlotRing<Staging> ring;
     // blocking host path
     rc::DevBuf d_data, d_out;
     rc::PairTimer timer;
@@ -46,30 +44,13 @@ struct rc_hasher {
 
 namespace {
 
-using Workspace = rc_hasher::Workspace;
-
-int acquire(rc_hasher *h, Workspace *&out) {
-    Workspace &w = h->ws[h->next_ws++ & 1];
-    if (w.pending) {  // its previous call must have consumed the staging
-        RC_HIP_TRY(hipEventSynchronize(w.done));
-        w.pending = false;
-    }
-    out = &w;
-    return 0;
-}
-
-int finish(rc_hasher *h, Workspace &w, hipStream_t st) {
-    RC_HIP_TRY(hipEventRecord(w.done, st));
-    w.pending = true;
-    (void)h;
-    return 0;
-}
+using Workspace = rc::SlotRing<rc_hasher::Staging>::Slot;
 
 // digest of n device buffers: items built on the host
 int enqueue_items(rc_hasher *h, uint64_t n, const uint8_t *const *d_ptrs, const uint64_t *lens,
                   uint8_t *d_out, hipStream_t st) {
     Workspace *w = nullptr;
-    if (int rc = acquire(h, w)) return rc;
+    if (int rc = h->ring.acquire(w)) return rc;
     const size_t bytes = n * sizeof(B2Item);
     if (int rc = w->h_stage.ensure(bytes)) return rc;
     if (int rc = w->d_stage.ensure(bytes)) return rc;
@@ -78,27 +59,20 @@ int enqueue_items(rc_hasher *h, uint64_t n, const uint8_t *const *d_ptrs, const 
     // longest first: the kernel deals items round-robin (see blake2b.hip)
     std::stable_sort(it, it + n, [](const B2Item &x, const B2Item &y) { return x.len > y.len; });
     RC_HIP_TRY(hipMemcpyAsync(w->d_stage.p, w->h_stage.p, bytes, hipMemcpyHostToDevice, st));
-    rc::PairTimer::Pair ev{};
-    if (int rc = h->timer.begin(st, ev)) return rc;
     uint64_t msg_bytes = 0;
     for (uint64_t i = 0; i < n; ++i) msg_bytes += lens[i];
     const B2Item *d_items = static_cast<const B2Item *>(w->d_stage.p);
-    if (h->algo == RC_HASH_SHA2) {
-        if (rc_sha2_launch_items(d_items, nullptr, n, n, h->digest_size, d_out,
-                                 rc_sha_lane_max(h->algo, msg_bytes, it[0].len, h->knobs[rc::knShaLaneMax]), st))
-            return rc_fail(RC_ERR_HIP, "%s", rc_sha_launch_error());
-    } else if (h->algo == RC_HASH_SHA3) {
-        if (rc_sha3_launch_items(d_items, nullptr, n, n, h->digest_size, d_out,
-                                 rc_sha_lane_max(h->algo, msg_bytes, it[0].len, h->knobs[rc::knShaLaneMax]), st))
-            return rc_fail(RC_ERR_HIP, "%s", rc_sha_launch_error());
-    } else {
-        const uint64_t lane_max = rc_b2_lane_max(msg_bytes, it[0].len, h->knobs[rc::knB2LaneMax]);
-        if (rc_b2_launch_items(d_items, n, h->digest_size, d_out, lane_max,
-                               rc_b2_lane_only(lane_max, it[0].len, h->knobs[rc::knB2LaneOnly] == 1), st))
-            return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
-    }
-    if (int rc = h->timer.end(st, ev)) return rc;
-    return finish(h, *w, st);
+    if (int rc = rc::timed(h->timer, st, [&] {
+            if (h->algo != RC_HASH_BLAKE2B)
+                return (h->algo == RC_HASH_SHA2 ? rc_sha2_launch_items : rc_sha3_launch_items)(
+                    d_items, nullptr, n, n, h->digest_size, d_out,
+                    rc_sha_lane_max(h->algo, msg_bytes, it[0].len, h->knobs[rc::knShaLaneMax]), st);
+            const uint64_t lane_max = rc_b2_lane_max(msg_bytes, it[0].len, h->knobs[rc::knB2LaneMax]);
+            return rc_b2_launch_items(d_items, n, h->digest_size, d_out, lane_max,
+                                      rc_b2_lane_only(lane_max, it[0].len, h->knobs[rc::knB2LaneOnly] == 1), st);
+        }))
+        return rc;
+    return h->ring.finish(*w, st);
 }
 
 // incremental updates: items built on the host
@@ -106,7 +80,7 @@ int enqueue_update(rc_hasher *h, uint64_t n, rc_blake2b_state *const *d_states,
                    const uint8_t *const *d_ptrs, const uint64_t *lens, const uint8_t *finals,
                    uint8_t *d_out, hipStream_t st) {
     Workspace *w = nullptr;
-    if (int rc = acquire(h, w)) return rc;
+    if (int rc = h->ring.acquire(w)) return rc;
     const size_t bytes = n * sizeof(B2UItem);
     if (int rc = w->h_stage.ensure(bytes)) return rc;
     if (int rc = w->d_stage.ensure(bytes)) return rc;
@@ -123,8 +97,7 @@ int enqueue_update(rc_hasher *h, uint64_t n, rc_blake2b_state *const *d_states,
         const size_t tb = 2 * n * sizeof(uint32_t);
         if (int rc = w->d_tags.ensure(tb)) return rc;
         if (int rc = w->h_tags.ensure(tb)) return rc;
-        if (rc_sha_launch_tags(d_items, n, static_cast<uint32_t *>(w->d_tags.p), st))
-            return rc_fail(RC_ERR_HIP, "%s", rc_sha_launch_error());
+        if (int rc = rc_sha_launch_tags(d_items, n, static_cast<uint32_t *>(w->d_tags.p), st)) return rc;
         RC_HIP_TRY(hipMemcpyAsync(w->h_tags.p, w->d_tags.p, tb, hipMemcpyDeviceToHost, st));
         RC_HIP_TRY(hipStreamSynchronize(st));
         const uint32_t *tg = static_cast<const uint32_t *>(w->h_tags.p);
@@ -134,19 +107,13 @@ int enqueue_update(rc_hasher *h, uint64_t n, rc_blake2b_state *const *d_states,
                                "this hasher's (algorithm %u, digest_size %u)", tg[2 * i + 1], tg[2 * i],
                                h->algo, h->digest_size);
     }
-    rc::PairTimer::Pair ev{};
-    if (int rc = h->timer.begin(st, ev)) return rc;
-    if (h->algo == RC_HASH_SHA2) {
-        if (rc_sha2_launch_update(d_items, n, h->digest_size, d_out, st))
-            return rc_fail(RC_ERR_HIP, "%s", rc_sha_launch_error());
-    } else if (h->algo == RC_HASH_SHA3) {
-        if (rc_sha3_launch_update(d_items, n, h->digest_size, d_out, st))
-            return rc_fail(RC_ERR_HIP, "%s", rc_sha_launch_error());
-    } else if (rc_b2_launch_update(d_items, n, d_out, st)) {
-        return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
-    }
-    if (int rc = h->timer.end(st, ev)) return rc;
-    return finish(h, *w, st);
+    if (int rc = rc::timed(h->timer, st, [&] {
+            if (h->algo == RC_HASH_SHA2) return rc_sha2_launch_update(d_items, n, h->digest_size, d_out, st);
+            if (h->algo == RC_HASH_SHA3) return rc_sha3_launch_update(d_items, n, h->digest_size, d_out, st);
+            return rc_b2_launch_update(d_items, n, d_out, st);
+        }))
+        return rc;
+    return h->ring.finish(*w, st);
 }
 
 int check_buffers(uint64_t n, const uint8_t *const *ptrs, const uint64_t *lens) {
@@ -167,7 +134,7 @@ int rc_hasher_enqueue_chunks(rc_hasher *h, uint64_t n, const uint8_t *const *d_p
     std::lock_guard<std::mutex> lock(h->mu);
     rc::DeviceGuard g(h->device);
     Workspace *w = nullptr;
-    if (int rc = acquire(h, w)) return rc;
+    if (int rc = h->ring.acquire(w)) return rc;
     // staging: ptr[n] cut_base[n] | device also: chunk_off[n+1], the sort histogram
     const size_t up = 2 * n * sizeof(uint64_t);
     const size_t hist_off = up + (n + 1) * sizeof(uint64_t);
@@ -182,26 +149,22 @@ int rc_hasher_enqueue_chunks(rc_hasher *h, uint64_t n, const uint8_t *const *d_p
     RC_HIP_TRY(hipMemcpyAsync(w->d_stage.p, w->h_stage.p, up, hipMemcpyHostToDevice, st));
     const uint64_t *d = static_cast<const uint64_t *>(w->d_stage.p);
     uint64_t *chunk_off = static_cast<uint64_t *>(w->d_stage.p) + 2 * n;
-    rc::PairTimer::Pair ev{};
-    if (int rc = h->timer.begin(st, ev)) return rc;
     uint32_t *hist = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(w->d_stage.p) + hist_off);
     B2Item *items = static_cast<B2Item *>(w->d_items.p);
-    if (h->algo != RC_HASH_BLAKE2B) {  // the same longest-first list, then one lane per chunk
-        if (rc_b2_launch_sort(n, d, d + n, d_cuts, d_counts, chunk_off, hist, items, st))
-            return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
-        const uint64_t lane_max = rc_sha_lane_max(h->algo, bytes, longest, h->knobs[rc::knShaLaneMax]);
-        const int bad = (h->algo == RC_HASH_SHA2 ? rc_sha2_launch_items : rc_sha3_launch_items)(
-            items, chunk_off + n, 0, total_cap, h->digest_size, d_out, lane_max, st);
-        if (bad) return rc_fail(RC_ERR_HIP, "%s", rc_sha_launch_error());
-    } else {
-        const uint64_t lane_max = rc_b2_lane_max(bytes, longest, h->knobs[rc::knB2LaneMax]);
-        if (rc_b2_launch_chunks(n, d, d + n, d_cuts, d_counts, chunk_off, hist, items, total_cap,
-                                h->digest_size, d_out, lane_max,
-                                rc_b2_lane_only(lane_max, longest, h->knobs[rc::knB2LaneOnly] == 1), st))
-            return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
-    }
-    if (int rc = h->timer.end(st, ev)) return rc;
-    return finish(h, *w, st);
+    if (int rc = rc::timed(h->timer, st, [&] {
+            if (h->algo != RC_HASH_BLAKE2B) {  // the same longest-first list, then one lane per chunk
+                if (int rc = rc_b2_launch_sort(n, d, d + n, d_cuts, d_counts, chunk_off, hist, items, st)) return rc;
+                const uint64_t lane_max = rc_sha_lane_max(h->algo, bytes, longest, h->knobs[rc::knShaLaneMax]);
+                return (h->algo == RC_HASH_SHA2 ? rc_sha2_launch_items : rc_sha3_launch_items)(
+                    items, chunk_off + n, 0, total_cap, h->digest_size, d_out, lane_max, st);
+            }
+            const uint64_t lane_max = rc_b2_lane_max(bytes, longest, h->knobs[rc::knB2LaneMax]);
+            return rc_b2_launch_chunks(n, d, d + n, d_cuts, d_counts, chunk_off, hist, items, total_cap,
+                                       h->digest_size, d_out, lane_max,
+                                       rc_b2_lane_only(lane_max, longest, h->knobs[rc::knB2LaneOnly] == 1), st);
+        }))
+        return rc;
+    return h->ring.finish(*w, st);
 }
 
 namespace {
@@ -213,21 +176,16 @@ static int create_hasher(uint32_t algo, uint32_t digest_size, int device, rc_has
     rc::Knobs knobs;
     if (rc::read_knobs(knobs, g_knob_err, sizeof g_knob_err))
         return rc_fail(RC_ERR_ARGUMENT, "%s", g_knob_err);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
-        return rc_fail(RC_ERR_NO_DEVICE, "no HIP device %d", device);
+    if (int rc = rc::check_device(device)) return rc;
     rc::DeviceGuard g(device);
     rc_hasher *h = new rc_hasher;
     h->knobs = knobs;
     h->algo = algo;
     h->digest_size = digest_size;
     h->device = device;
-    for (auto &w : h->ws) {
-        const hipError_t e = hipEventCreateWithFlags(&w.done, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            rc_blake2b_destroy(h);
-            return rc_fail(RC_ERR_HIP, "hipEventCreate failed: %s", hipGetErrorString(e));
-        }
+    if (int rc = h->ring.create()) {
+        rc_blake2b_destroy(h);
+        return rc;
     }
     rc_track(h, [](void *p) { rc_blake2b_destroy(static_cast<rc_hasher *>(p)); });
     *out = h;
@@ -262,25 +220,18 @@ int rc_sha3_create(uint32_t bits, int device, rc_hasher **out) {
 
 void rc_blake2b_destroy(rc_hasher *h) {
     if (!h) return;
-    rc_untrack(h);
-    {
-        // a call still running on another thread (a daemon thread when the exit hook runs)
-        // finishes first: its buffers and streams go only after it
-        std::lock_guard<std::mutex> lock(h->mu);
-        rc::DeviceGuard g(h->device);
-        (void)hipDeviceSynchronize();
-        for (auto &w : h->ws) {
+    rc::teardown(h, [h] {
+        h->ring.release([](rc_hasher::Staging &w) {
             w.h_stage.release();
             w.d_stage.release();
             w.d_items.release();
             w.d_tags.release();
             w.h_tags.release();
-            if (w.done) (void)hipEventDestroy(w.done);
-        }
+        });
         h->d_data.release();
         h->d_out.release();
         h->timer.release();
-    }
+    });
     delete h;
 }
 
@@ -311,12 +262,8 @@ int rc_blake2b_host(rc_hasher *h, uint64_t n, const uint8_t *const *ptrs, const 
     if (int rc = check_buffers(n, ptrs, lens)) return rc;
     std::lock_guard<std::mutex> lock(h->mu);
     rc::DeviceGuard g(h->device);
-    std::vector<uint64_t> off(n);
-    uint64_t total = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        off[i] = total;
-        total += (lens[i] + 15) & ~15ull;
-    }
+    std::vector<uint64_t> off;
+    const uint64_t total = rc::offsets16(n, lens, off);
     if (int rc = h->d_data.ensure(total + 16)) return rc;
     if (int rc = h->d_out.ensure(n * kB2Slot)) return rc;
     std::vector<const uint8_t *> dp(n);
@@ -433,7 +380,7 @@ int rc_blake2b_derive_chunks(rc_hasher *h, const rc_chunker *layout, uint64_t n,
     rc::DeviceGuard g(h->device);
     const hipStream_t st = static_cast<hipStream_t>(hip_stream);
     Workspace *w = nullptr;
-    if (int rc = acquire(h, w)) return rc;
+    if (int rc = h->ring.acquire(w)) return rc;
     const size_t bytes = n * sizeof(uint64_t);
     if (int rc = w->h_stage.ensure(bytes)) return rc;
     if (int rc = w->d_stage.ensure(bytes)) return rc;
@@ -444,26 +391,22 @@ int rc_blake2b_derive_chunks(rc_hasher *h, const rc_chunker *layout, uint64_t n,
         acc += caps[i];
     }
     RC_HIP_TRY(hipMemcpyAsync(w->d_stage.p, u, bytes, hipMemcpyHostToDevice, st));
-    rc::PairTimer::Pair ev{};
-    if (int rc = h->timer.begin(st, ev)) return rc;
-    if (rc_b2_launch_derive(n, static_cast<const uint64_t *>(w->d_stage.p), d_counts, d_kdf_state,
-                            d_digests, msg_len, d_keys, st))
-        return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
-    if (int rc = h->timer.end(st, ev)) return rc;
-    return finish(h, *w, st);
+    if (int rc = rc::timed(h->timer, st, [&] {
+            return rc_b2_launch_derive(n, static_cast<const uint64_t *>(w->d_stage.p), d_counts, d_kdf_state,
+                                       d_digests, msg_len, d_keys, st);
+        }))
+        return rc;
+    return h->ring.finish(*w, st);
 }
 
 int rc_blake2b_timing_enable(rc_hasher *h, int enable) {
     if (!h) return rc_fail(RC_ERR_ARGUMENT, "null hasher");
-    h->timer.enabled = enable != 0;
-    return RC_OK;
+    return rc::timing_enable(h, {&h->timer}, enable);
 }
 
 int rc_blake2b_timing_read(rc_hasher *h, double *ms, uint64_t *calls) {
     if (!h) return rc_fail(RC_ERR_ARGUMENT, "null hasher");
-    std::lock_guard<std::mutex> lock(h->mu);
-    rc::DeviceGuard g(h->device);
-    return h->timer.read(ms, calls);
+    return rc::timing_read(h, h->timer, ms, calls);
 }
 
 int rc_sha2_state_init(uint32_t bits, rc_sha2_state *out) {

@@ -31,15 +31,6 @@ struct rc_gc {
 
 namespace {
 
-// One group of launches (`launch` returns gc.hip's status) inside timer t's event pair.
-template <class F>
-int timed_launch(rc::PairTimer &t, hipStream_t st, F launch) {
-    rc::PairTimer::Pair ev{};
-    if (int rc = t.begin(st, ev)) return rc;
-    if (launch()) return rc_fail(RC_ERR_HIP, "%s", rc_gc_launch_error());
-    return t.end(st, ev);
-}
-
 void destroy_tracked(void *p) { rc_gc_destroy(static_cast<rc_gc *>(p)); }
 
 // n items of `bytes` bytes, back to back, as zero-padded 64-byte slots.
@@ -69,7 +60,7 @@ int stage_digests(rc_gc *g, const uint8_t *digests, uint64_t nb, std::vector<uin
     if (!g->d_mac) return 0;
     if (int rc = g->d_names.ensure(image.size())) return rc;
     const uint8_t *d_digests = *d_keys;
-    if (int rc = timed_launch(g->t_names, nullptr, [&] {
+    if (int rc = rc::timed(g->t_names, nullptr, [&] {
             return rc_gc_launch_names(g->d_mac, nb, d_digests, g->digest_bytes, true, nullptr, 0,
                                       static_cast<uint8_t *>(g->d_names.p), nullptr, nullptr);
         }))
@@ -103,11 +94,11 @@ int sweep_enqueue(rc_gc *g, uint64_t n, const uint8_t *d_names, const uint8_t *d
     IndexView v;
     if (int rc = rc_index_view(g->index, &v)) return rc;
     if (int rc = g->d_scratch.ensure(rc_gc_scratch_words(n) * sizeof(uint64_t))) return rc;
-    if (int rc = timed_launch(g->t_sweep, st, [&] {
+    if (int rc = rc::timed(g->t_sweep, st, [&] {
             return rc_gc_launch_sweep(v, g->d_mac, n, d_names, d_tags, d_verdict, st);
         }))
         return rc;
-    return timed_launch(g->t_compact, st, [&] {
+    return rc::timed(g->t_compact, st, [&] {
         return rc_gc_launch_compact(d_verdict, n, kGcDelete, index_base, static_cast<uint64_t *>(g->d_scratch.p),
                                     d_delete_idx, d_n_delete, st);
     });
@@ -131,9 +122,7 @@ int rc_gc_create(uint32_t digest_bytes, uint32_t name_bytes, const uint8_t *mac_
         return rc_fail(RC_ERR_ARGUMENT, "unkeyed: name_bytes %u must equal digest_bytes %u", name_bytes,
                        digest_bytes);
     if (max_refs > (uint64_t(1) << 40)) return rc_fail(RC_ERR_ARGUMENT, "max_refs above 2^40");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
-        return rc_fail(RC_ERR_NO_DEVICE, "no HIP device %d", device);
+    if (int rc = rc::check_device(device)) return rc;
     rc::DeviceGuard guard(device);
     rc_gc *g = new rc_gc;
     g->device = device;
@@ -162,26 +151,20 @@ int rc_gc_create(uint32_t digest_bytes, uint32_t name_bytes, const uint8_t *mac_
 
 void rc_gc_destroy(rc_gc *g) {
     if (!g) return;
-    rc_untrack(g);
-    {
-        std::lock_guard<std::mutex> lock(g->mu);
-        rc::DeviceGuard guard(g->device);
-        (void)hipDeviceSynchronize();
+    rc::teardown(g, [g] {
         rc_index_destroy(g->index);
         if (g->d_mac) (void)hipFree(g->d_mac);
         for (rc::DevBuf *b : {&g->d_scratch, &g->d_total, &g->d_in, &g->d_names, &g->d_tags, &g->d_sel_names,
                               &g->d_verdict, &g->d_idx, &g->d_owner, &g->d_fresh})
             b->release();
         for (rc::PairTimer *t : {&g->t_names, &g->t_sweep, &g->t_compact}) t->release();
-    }
+    });
     delete g;
 }
 
 int rc_gc_timing_enable(rc_gc *g, int enable) {
     if (!g) return rc_fail(RC_ERR_ARGUMENT, "null gc");
-    std::lock_guard<std::mutex> lock(g->mu);
-    for (rc::PairTimer *t : {&g->t_names, &g->t_sweep, &g->t_compact}) t->enabled = enable != 0;
-    return RC_OK;
+    return rc::timing_enable(g, {&g->t_names, &g->t_sweep, &g->t_compact}, enable);
 }
 
 int rc_gc_timing_read(rc_gc *g, double *names_ms, double *sweep_ms, double *compact_ms, uint64_t *calls) {
@@ -290,7 +273,7 @@ int rc_gc_unreferenced_host(rc_gc *g, uint64_t n, const uint8_t *digests, uint64
         // the fresh ones, in order: unreferenced, and the first of their digest
         if (int rc = g->d_scratch.ensure(rc_gc_scratch_words(nb) * sizeof(uint64_t))) return rc;
         if (int rc = g->d_idx.ensure(nb * sizeof(uint64_t))) return rc;
-        if (int rc = timed_launch(g->t_compact, nullptr, [&] {
+        if (int rc = rc::timed(g->t_compact, nullptr, [&] {
                 return rc_gc_launch_compact(static_cast<const uint8_t *>(g->d_fresh.p), nb, 1, off,
                                             static_cast<uint64_t *>(g->d_scratch.p),
                                             static_cast<uint64_t *>(g->d_idx.p),
@@ -310,7 +293,7 @@ int rc_gc_unreferenced_host(rc_gc *g, uint64_t n, const uint8_t *digests, uint64
         } else {  // the survivors' names gathered, and their tags
             for (rc::DevBuf *b : {&g->d_sel_names, &g->d_tags})
                 if (int rc = b->ensure(total * kIndexSlot)) return rc;
-            if (int rc = timed_launch(g->t_names, nullptr, [&] {
+            if (int rc = rc::timed(g->t_names, nullptr, [&] {
                     return rc_gc_launch_names(g->d_mac, total, d_keys, nb_name, false,
                                               static_cast<const uint64_t *>(g->d_idx.p), off,
                                               static_cast<uint8_t *>(g->d_sel_names.p),

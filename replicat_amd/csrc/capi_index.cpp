@@ -19,14 +19,12 @@ struct rc_index {
     uint8_t *pool = nullptr;
     uint64_t *table = nullptr;
     std::mutex mu;
-    // a call's cut_base list: two staging pairs, alternating, each guarded by its call's event
-    struct Workspace {
+    // a call's cut_base list
+    struct Staging {
         rc::PinnedBuf h_stage;
         rc::DevBuf d_stage;
-        hipEvent_t done = nullptr;
-        bool pending = false;
-    } ws[2];
-    unsigned next_ws = 0;
+    };
+    rc::SlotRing<Staging> ring;
 };
 
 namespace {
@@ -56,6 +54,14 @@ int allocate(uint64_t max_names, uint8_t **pool, uint64_t **table, uint64_t *ent
 
 void destroy_tracked(void *p) { rc_index_destroy(static_cast<rc_index *>(p)); }
 
+// Stage the work's names, insert them and resolve every slot's owner.
+int resolve_work(const IndexView &v, const IndexWork &work, const uint8_t *d_names, int64_t *d_owner,
+                 uint8_t *d_fresh, hipStream_t st) {
+    if (int rc = rc_index_launch_stage(v, work, d_names, st)) return rc;
+    if (int rc = rc_index_launch_insert(v, work, st)) return rc;
+    return rc_index_launch_resolve(v, work, d_owner, d_fresh, st);
+}
+
 int check_room(const rc_index *x, uint64_t more) {
     if (more > x->max_names || x->used > x->max_names - more)
         return rc_fail(RC_ERR_INDEX_FULL, "index full: %llu ids used, %llu more exceed max_names %llu",
@@ -74,18 +80,14 @@ int rc_index_create(uint32_t name_bytes, uint64_t max_names, int device, rc_inde
     if (name_bytes < 1 || name_bytes > kIndexSlot)
         return rc_fail(RC_ERR_ARGUMENT, "name_bytes must be 1..64, not %u", name_bytes);
     if (max_names > (uint64_t(1) << 40)) return rc_fail(RC_ERR_ARGUMENT, "max_names above 2^40");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
-        return rc_fail(RC_ERR_NO_DEVICE, "no HIP device %d", device);
+    if (int rc = rc::check_device(device)) return rc;
     rc::DeviceGuard guard(device);
     rc_index *x = new rc_index;
     x->device = device;
     x->name_bytes = name_bytes;
     x->max_names = max_names;
     int rc = allocate(max_names, &x->pool, &x->table, &x->entries);
-    for (auto &w : x->ws)
-        if (!rc && hipEventCreateWithFlags(&w.done, hipEventDisableTiming) != hipSuccess)
-            rc = rc_fail(RC_ERR_HIP, "hipEventCreate failed");
+    if (!rc) rc = x->ring.create();
     if (rc) {
         rc_index_destroy(x);  // frees whatever was allocated; untracking an untracked handle is a no-op
         return rc;
@@ -97,19 +99,14 @@ int rc_index_create(uint32_t name_bytes, uint64_t max_names, int device, rc_inde
 
 void rc_index_destroy(rc_index *x) {
     if (!x) return;
-    rc_untrack(x);
-    {
-        std::lock_guard<std::mutex> lock(x->mu);
-        rc::DeviceGuard guard(x->device);
-        (void)hipDeviceSynchronize();
+    rc::teardown(x, [x] {
         if (x->pool) (void)hipFree(x->pool);
         if (x->table) (void)hipFree(x->table);
-        for (auto &w : x->ws) {
+        x->ring.release([](rc_index::Staging &w) {
             w.h_stage.release();
             w.d_stage.release();
-            if (w.done) (void)hipEventDestroy(w.done);
-        }
-    }
+        });
+    });
     delete x;
 }
 
@@ -132,7 +129,7 @@ int rc_index_add_host(rc_index *x, uint64_t n, const uint8_t *names, uint64_t *f
     RC_HIP_TRY(hipDeviceSynchronize());  // the index's outstanding work, on whatever stream
     RC_HIP_TRY(hipMemcpy(x->pool + kIndexSlot * x->used, image.data(), image.size(), hipMemcpyHostToDevice));
     const IndexWork w{nullptr, nullptr, 0, n, x->used};
-    if (rc_index_launch_insert(view_of(x), w, nullptr)) return rc_fail(RC_ERR_HIP, "%s", rc_index_launch_error());
+    if (int rc = rc_index_launch_insert(view_of(x), w, nullptr)) return rc;
     RC_HIP_TRY(hipDeviceSynchronize());
     x->used += n;
     return RC_OK;
@@ -157,28 +154,21 @@ int rc_index_resolve_chunks(rc_index *x, const rc_chunker *layout, uint64_t n, c
     if (int rc = check_room(x, slots)) return rc;
     rc::DeviceGuard guard(x->device);
     const hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    rc_index::Workspace &w = x->ws[x->next_ws++ & 1];
-    if (w.pending) {  // its previous call must have consumed the staging
-        RC_HIP_TRY(hipEventSynchronize(w.done));
-        w.pending = false;
-    }
+    rc::SlotRing<rc_index::Staging>::Slot *w = nullptr;
+    if (int rc = x->ring.acquire(w)) return rc;
     const size_t bytes = n * sizeof(uint64_t);
-    if (int rc = w.h_stage.ensure(bytes)) return rc;
-    if (int rc = w.d_stage.ensure(bytes)) return rc;
-    uint64_t *u = static_cast<uint64_t *>(w.h_stage.p);
+    if (int rc = w->h_stage.ensure(bytes)) return rc;
+    if (int rc = w->d_stage.ensure(bytes)) return rc;
+    uint64_t *u = static_cast<uint64_t *>(w->h_stage.p);
     uint64_t acc = 0;
     for (uint64_t i = 0; i < n; ++i) {
         u[i] = acc;
         acc += caps[i];
     }
-    RC_HIP_TRY(hipMemcpyAsync(w.d_stage.p, u, bytes, hipMemcpyHostToDevice, st));
-    const IndexView v = view_of(x);
-    const IndexWork work{static_cast<const uint64_t *>(w.d_stage.p), d_counts, n, slots, x->used};
-    if (rc_index_launch_stage(v, work, d_names, st) || rc_index_launch_insert(v, work, st) ||
-        rc_index_launch_resolve(v, work, d_owner, d_fresh, st))
-        return rc_fail(RC_ERR_HIP, "%s", rc_index_launch_error());
-    RC_HIP_TRY(hipEventRecord(w.done, st));
-    w.pending = true;
+    RC_HIP_TRY(hipMemcpyAsync(w->d_stage.p, u, bytes, hipMemcpyHostToDevice, st));
+    const IndexWork work{static_cast<const uint64_t *>(w->d_stage.p), d_counts, n, slots, x->used};
+    if (int rc = resolve_work(view_of(x), work, d_names, d_owner, d_fresh, st)) return rc;
+    if (int rc = x->ring.finish(*w, st)) return rc;
     x->used += slots;
     return RC_OK;
 }
@@ -192,9 +182,7 @@ int rc_index_lookup_device(rc_index *x, uint64_t n, const uint8_t *d_names, int6
         return rc_fail(RC_ERR_ALIGN, "d_names is not 8-byte aligned");
     std::lock_guard<std::mutex> lock(x->mu);
     rc::DeviceGuard guard(x->device);
-    if (rc_index_launch_lookup(view_of(x), n, d_names, d_owner, static_cast<hipStream_t>(hip_stream)))
-        return rc_fail(RC_ERR_HIP, "%s", rc_index_launch_error());
-    return RC_OK;
+    return rc_index_launch_lookup(view_of(x), n, d_names, d_owner, static_cast<hipStream_t>(hip_stream));
 }
 
 int rc_index_resolve_names_device(rc_index *x, uint64_t n, const uint8_t *d_names, uint64_t *id_base,
@@ -213,11 +201,8 @@ int rc_index_resolve_names_device(rc_index *x, uint64_t n, const uint8_t *d_name
     if (int rc = check_room(x, n)) return rc;
     rc::DeviceGuard guard(x->device);
     const hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const IndexView v = view_of(x);
     const IndexWork work{nullptr, nullptr, 0, n, x->used};  // flat: every lane carries a name
-    if (rc_index_launch_stage(v, work, d_names, st) || rc_index_launch_insert(v, work, st) ||
-        rc_index_launch_resolve(v, work, d_owner, d_fresh, st))
-        return rc_fail(RC_ERR_HIP, "%s", rc_index_launch_error());
+    if (int rc = resolve_work(view_of(x), work, d_names, d_owner, d_fresh, st)) return rc;
     x->used += n;
     return RC_OK;
 }
@@ -236,8 +221,7 @@ int rc_index_reserve(rc_index *x, uint64_t max_names) {
     if (x->used && hipMemcpy(pool, x->pool, x->used * kIndexSlot, hipMemcpyDeviceToDevice) != hipSuccess)
         rc = rc_fail(RC_ERR_HIP, "hipMemcpy of the pool failed");
     const IndexView v{pool, table, entries - 1, x->name_bytes};
-    if (!rc && rc_index_launch_reinsert(v, x->table, x->entries, nullptr))
-        rc = rc_fail(RC_ERR_HIP, "%s", rc_index_launch_error());
+    if (!rc) rc = rc_index_launch_reinsert(v, x->table, x->entries, nullptr);
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = rc_fail(RC_ERR_HIP, "hipDeviceSynchronize failed");
     if (rc) {
         (void)hipFree(pool);

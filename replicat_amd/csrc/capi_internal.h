@@ -1,12 +1,16 @@
-// capi_internal.h -- what the host files (capi.cpp: chunker, capi_digest.cpp: BLAKE2b,
-// cipher_host.cpp and its two ciphers) share: the error slot, the live-handle registry, the
-// device guard, the growable buffers and the event-pair timer.
+// capi_internal.h -- the handle core every family's host file shares (capi.cpp: chunker,
+// capi_digest.cpp: hashers, cipher_host.cpp and its two ciphers, capi_restore.cpp, capi_index.cpp,
+// capi_gc.cpp) and the launchers in the .hip files report through: the error slot and the launch
+// status, the live-handle registry, the device check and guard, the growable buffers, the
+// two-slot staging ring, the event-pair timer and the shared half of *_destroy and *_timing_*.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 #include <array>
+#include <initializer_list>
+#include <mutex>
 #include <vector>
 
 #include "../../include/replicat_digest.h"
@@ -31,6 +35,36 @@ void rc_untrack(void *handle);
     } while (0)
 
 namespace rc {
+
+// After a kernel launch: 0, or the calling thread's RC_ERR_HIP failure "<what>: <HIP's text>".
+// Every rc_*_launch_* function returns such a code.
+inline int launch_status(const char *what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : rc_fail(RC_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+}
+
+// A *_create's device check (it reads no environment knob: the creators that parse them do so
+// themselves).
+inline int check_device(int device) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
+        return rc_fail(RC_ERR_NO_DEVICE, "no HIP device %d", device);
+    return 0;
+}
+
+inline uint64_t up16(uint64_t x) { return (x + 15) & ~uint64_t(15); }
+
+// off[i] = where buffer i of lens[i] bytes starts when the n buffers lie back to back, each
+// 16-aligned (the blocking host paths' device image); returns the image's length.
+inline uint64_t offsets16(uint64_t n, const uint64_t *lens, std::vector<uint64_t> &off) {
+    off.resize(n);
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        off[i] = total;
+        total += up16(lens[i]);
+    }
+    return total;
+}
 
 // Makes `dev` the calling thread's device for a scope.
 struct DeviceGuard {
@@ -140,6 +174,95 @@ struct PairTimer {
         pool.clear();
     }
 };
+
+// One group of enqueued work (`body` returns 0 or an rc_fail code) inside timer t's event pair.
+template <class F>
+int timed(PairTimer &t, hipStream_t st, F body) {
+    PairTimer::Pair ev{};
+    if (int rc = t.begin(st, ev)) return rc;
+    if (int rc = body()) return rc;
+    return t.end(st, ev);
+}
+
+// A handle's per-call staging: two slots of the family's buffers `Bufs`, used alternately so
+// that two calls can be in flight.  A slot is taken again only after the event of the call that
+// last used it; every enqueue ends with finish(), which records that event.  The caller holds
+// the handle's lock and has its device current.
+template <class Bufs>
+class SlotRing {
+public:
+    class Slot : public Bufs {
+        friend class SlotRing;
+        hipEvent_t done = nullptr;
+        bool pending = false;
+    };
+    int create() {
+        for (auto &s : slots) RC_HIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+        return 0;
+    }
+    // The next slot, once its previous call has consumed it; on_wait(slot index) runs before a wait.
+    template <class OnWait>
+    int acquire(Slot *&out, OnWait on_wait) {
+        const unsigned i = next_ws++ & 1;
+        Slot &s = slots[i];
+        if (s.pending) {
+            on_wait(i);
+            RC_HIP_TRY(hipEventSynchronize(s.done));
+            s.pending = false;
+        }
+        out = &s;
+        return 0;
+    }
+    int acquire(Slot *&out) {
+        return acquire(out, [](unsigned) {});
+    }
+    int finish(Slot &s, hipStream_t st) {
+        RC_HIP_TRY(hipEventRecord(s.done, st));
+        s.pending = true;
+        return 0;
+    }
+    // f(buffers) frees each slot's buffers; the device is idle (teardown below).
+    template <class F>
+    void release(F f) {
+        for (auto &s : slots) {
+            f(static_cast<Bufs &>(s));
+            if (s.done) (void)hipEventDestroy(s.done);
+            s.done = nullptr;
+        }
+    }
+
+private:
+    Slot slots[2];
+    unsigned next_ws = 0;
+};
+
+// The shared half of every *_destroy of a handle with a lock `mu` and a `device`: leaves the
+// live-handle registry, then, with the device current and idle, lets `release` free what the
+// handle owns.  The caller deletes the handle.
+template <class H, class F>
+void teardown(H *h, F release) {
+    rc_untrack(h);
+    // a call still running on another thread (a daemon thread when the exit hook runs)
+    // finishes first: its buffers and streams go only after it
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard guard(h->device);
+    (void)hipDeviceSynchronize();
+    release();
+}
+
+// Behind *_timing_enable and the one-timer *_timing_read (the caller has checked h).
+template <class H>
+int timing_enable(H *h, std::initializer_list<PairTimer *> timers, int enable) {
+    std::lock_guard<std::mutex> lock(h->mu);
+    for (PairTimer *t : timers) t->enabled = enable != 0;
+    return RC_OK;
+}
+template <class H>
+int timing_read(H *h, PairTimer &t, double *ms, uint64_t *calls) {
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard guard(h->device);
+    return t.read(ms, calls);
+}
 
 }  // namespace rc
 

@@ -26,14 +26,12 @@ struct rc_restore {
     uint32_t digest_size = 0, overhead = 0;
     std::mutex mu;
     rc::DevBuf d_kdf;  // the rc_blake2b_state of the shared-subkey KDF
-    struct Workspace {
+    struct Staging {
         rc::PinnedBuf h_stage;  // B2UItem[n] (the KDF's work list) | RestorePlain[n]
         rc::DevBuf d_stage;     // their device copy
         rc::DevBuf d_scratch;   // keys[64 n] | digests[64 n] | ok[n]
-        hipEvent_t done = nullptr;
-        bool pending = false;
-    } ws[2];
-    unsigned next_ws = 0;
+    };
+    rc::SlotRing<Staging> ring;  // (a slot's previous call also consumed its scratch)
     // blocking host path
     rc::DevBuf d_in, d_out, d_meta;  // blobs | plaintexts | expected[64 n] status[n]
     rc::PairTimer timer;
@@ -41,19 +39,7 @@ struct rc_restore {
 
 namespace {
 
-using Workspace = rc_restore::Workspace;
-
-uint64_t up16(uint64_t x) { return (x + 15) & ~uint64_t(15); }
-
-int acquire(rc_restore *r, Workspace *&out) {
-    Workspace &w = r->ws[r->next_ws++ & 1];
-    if (w.pending) {  // its previous call must have consumed the staging and the scratch
-        RC_HIP_TRY(hipEventSynchronize(w.done));
-        w.pending = false;
-    }
-    out = &w;
-    return 0;
-}
+using rc::up16;
 
 // the caller holds r->mu and has the device current
 int verify_locked(rc_restore *r, uint64_t n, const uint8_t *const *d_blobs, const uint64_t *blob_lens,
@@ -62,8 +48,8 @@ int verify_locked(rc_restore *r, uint64_t n, const uint8_t *const *d_blobs, cons
     const bool enc = r->cipher != nullptr;
     std::vector<uint64_t> plain_lens(n);
     for (uint64_t i = 0; i < n; ++i) plain_lens[i] = blob_lens[i] > r->overhead ? blob_lens[i] - r->overhead : 0;
-    Workspace *w = nullptr;
-    if (int rc = acquire(r, w)) return rc;
+    rc::SlotRing<rc_restore::Staging>::Slot *w = nullptr;
+    if (int rc = r->ring.acquire(w)) return rc;
     const size_t plain_off = up16(n * sizeof(B2UItem));
     const size_t stage = enc ? plain_off + n * sizeof(RestorePlain) : 0;
     if (int rc = w->d_scratch.ensure(n * (2 * kB2Slot + 1))) return rc;
@@ -88,18 +74,6 @@ int verify_locked(rc_restore *r, uint64_t n, const uint8_t *const *d_blobs, cons
         d_items = static_cast<const B2UItem *>(w->d_stage.p);
         d_wipe = reinterpret_cast<const RestorePlain *>(static_cast<uint8_t *>(w->d_stage.p) + plain_off);
     }
-    rc::PairTimer::Pair ev{};
-    if (int rc = r->timer.begin(st, ev)) return rc;
-    if (enc) {
-        if (rc_b2_launch_update(d_items, n, d_keys, st)) return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
-        std::vector<const uint8_t *> keys(n);
-        for (uint64_t i = 0; i < n; ++i) keys[i] = d_keys + kB2Slot * i;
-        if (int rc = rc_cipher::decrypt_device(r->cipher, n, d_blobs, blob_lens, keys.data(), d_plain, d_ok, st))
-            return rc;
-        if (int rc = rc_hash_device(r->hasher, n, d_plain, plain_lens.data(), d_digests, st)) return rc;
-    } else if (int rc = rc_hash_device(r->hasher, n, d_blobs, blob_lens, d_digests, st)) {
-        return rc;
-    }
     RestoreVerdictArgs a{};
     a.ok = enc ? d_ok : nullptr;
     a.computed = d_digests;
@@ -108,11 +82,21 @@ int verify_locked(rc_restore *r, uint64_t n, const uint8_t *const *d_blobs, cons
     a.status = d_status;
     a.n = n;
     a.digest_size = r->digest_size;
-    if (rc_restore_launch_verdict(a, st)) return rc_fail(RC_ERR_HIP, "%s", rc_restore_launch_error());
-    if (int rc = r->timer.end(st, ev)) return rc;
-    RC_HIP_TRY(hipEventRecord(w->done, st));
-    w->pending = true;
-    return RC_OK;
+    if (int rc = rc::timed(r->timer, st, [&] {
+            if (enc) {
+                if (int rc = rc_b2_launch_update(d_items, n, d_keys, st)) return rc;
+                std::vector<const uint8_t *> keys(n);
+                for (uint64_t i = 0; i < n; ++i) keys[i] = d_keys + kB2Slot * i;
+                if (int rc = rc_cipher::decrypt_device(r->cipher, n, d_blobs, blob_lens, keys.data(), d_plain, d_ok, st))
+                    return rc;
+                if (int rc = rc_hash_device(r->hasher, n, d_plain, plain_lens.data(), d_digests, st)) return rc;
+            } else if (int rc = rc_hash_device(r->hasher, n, d_blobs, blob_lens, d_digests, st)) {
+                return rc;
+            }
+            return rc_restore_launch_verdict(a, st);
+        }))
+        return rc;
+    return r->ring.finish(*w, st);
 }
 
 int check_lists(const rc_restore *r, uint64_t n, const uint8_t *const *blobs, const uint64_t *lens,
@@ -163,7 +147,7 @@ int rc_restore_create(rc_hasher *hasher, int cipher, void *cipher_handle,
     r->digest_size = rc_hash_digest_size(hasher);
     r->overhead = core ? core->desc.nonce_bytes + 16 : 0;
     auto setup = [r, kdf_state]() -> int {
-        for (auto &w : r->ws) RC_HIP_TRY(hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
+        if (int rc = r->ring.create()) return rc;
         if (r->cipher) {
             if (int rc = r->d_kdf.ensure(sizeof *kdf_state)) return rc;
             RC_HIP_TRY(hipMemcpy(r->d_kdf.p, kdf_state, sizeof *kdf_state, hipMemcpyHostToDevice));
@@ -181,24 +165,18 @@ int rc_restore_create(rc_hasher *hasher, int cipher, void *cipher_handle,
 
 void rc_restore_destroy(rc_restore *r) {
     if (!r) return;
-    rc_untrack(r);
-    {
-        // a call still running on another thread finishes first (as the other families do)
-        std::lock_guard<std::mutex> lock(r->mu);
-        rc::DeviceGuard guard(r->device);
-        (void)hipDeviceSynchronize();
-        for (auto &w : r->ws) {
+    rc::teardown(r, [r] {
+        r->ring.release([](rc_restore::Staging &w) {
             w.h_stage.release();
             w.d_stage.release();
             w.d_scratch.release();
-            if (w.done) (void)hipEventDestroy(w.done);
-        }
+        });
         r->d_kdf.release();
         r->d_in.release();
         r->d_out.release();
         r->d_meta.release();
         r->timer.release();
-    }
+    });
     delete r;
 }
 
@@ -225,12 +203,8 @@ int rc_restore_verify_host(rc_restore *r, uint64_t n, const uint8_t *const *blob
     rc::DeviceGuard guard(r->device);
     const bool enc = r->cipher != nullptr;
     // blob i and its plaintext share an offset (16-aligned: AES-GCM's vector path)
-    std::vector<uint64_t> off(n);
-    uint64_t total = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        off[i] = total;
-        total += up16(lens[i]);
-    }
+    std::vector<uint64_t> off;
+    const uint64_t total = rc::offsets16(n, lens, off);
     if (int rc = r->d_in.ensure(total + 16)) return rc;
     if (enc)
         if (int rc = r->d_out.ensure(total + 16)) return rc;
@@ -266,15 +240,12 @@ int rc_restore_verify_host(rc_restore *r, uint64_t n, const uint8_t *const *blob
 
 int rc_restore_timing_enable(rc_restore *r, int enable) {
     if (!r) return rc_fail(RC_ERR_ARGUMENT, "null restore handle");
-    r->timer.enabled = enable != 0;
-    return RC_OK;
+    return rc::timing_enable(r, {&r->timer}, enable);
 }
 
 int rc_restore_timing_read(rc_restore *r, double *ms, uint64_t *calls) {
     if (!r) return rc_fail(RC_ERR_ARGUMENT, "null restore handle");
-    std::lock_guard<std::mutex> lock(r->mu);
-    rc::DeviceGuard guard(r->device);
-    return r->timer.read(ms, calls);
+    return rc::timing_read(r, r->timer, ms, calls);
 }
 
 }  // extern "C"

@@ -56,6 +56,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "capi_internal.h"
 #include "chacha_kernels.h"
 #include "poly1305_limbs.h"
 
@@ -412,12 +413,6 @@ __global__ __launch_bounds__(kChaThreads) void rc_chacha_kernel(ChaArgs a) {
     }
 }
 
-namespace {
-thread_local char g_cha_err[256];
-}  // namespace
-
-const char *rc_chacha_launch_error(void) { return g_cha_err; }
-
 int rc_chacha_launch(int mode, ChaArgs args, hipStream_t stream) {
     // A grid holds fewer than 2^32 threads, so a long list goes out in slices of kChaLaunchItems
     // items (1.25 workgroups of 256 threads per item: 2.7 G threads).  With the count on the
@@ -434,13 +429,9 @@ int rc_chacha_launch(int mode, ChaArgs args, hipStream_t stream) {
             case kChaEncrypt: rc_chacha_kernel<kChaEncrypt><<<grid, kChaThreads, 0, stream>>>(args); break;
             case kChaDecrypt: rc_chacha_kernel<kChaDecrypt><<<grid, kChaThreads, 0, stream>>>(args); break;
             case kChaPoly: rc_chacha_kernel<kChaPoly><<<grid, kChaThreads, 0, stream>>>(args); break;
-            default: snprintf(g_cha_err, sizeof g_cha_err, "bad mode %d", mode); return 1;
+            default: return rc_fail(RC_ERR_HIP, "bad mode %d", mode);
         }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            snprintf(g_cha_err, sizeof g_cha_err, "rc_chacha_kernel: %s", hipGetErrorString(e));
-            return 1;
-        }
+        if (int rc = rc::launch_status("rc_chacha_kernel")) return rc;
     }
     return 0;
 }

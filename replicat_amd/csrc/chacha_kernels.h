@@ -30,7 +30,6 @@ constexpr uint64_t kChaWaveMax = 8192;    // items up to this long take one wave
 constexpr uint64_t kChaMaxLen = 0xFFFFFFFFull * 64;  // RFC 8439 §2.8: the 32-bit block counter
 constexpr uint64_t kChaLaunchItems = 1ull << 23;     // items per launch: its grid stays below 2^32 threads
 
-const char *rc_chacha_launch_error(void);
 
 // Over n items (or the bound of *d_total), kChaLaunchItems per launch: ceil(items / 4)
 // wave-per-item workgroups, then `items` workgroup-per-item ones; each item is taken by exactly

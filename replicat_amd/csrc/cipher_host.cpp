@@ -46,9 +46,9 @@ void StagingBuf::release() {
 
 namespace {
 
-using Workspace = CipherCore::Workspace;
+using Workspace = rc::SlotRing<CipherCore::Staging>::Slot;
+using rc::up16;
 
-uint64_t up16(uint64_t x) { return (x + 15) & ~uint64_t(15); }
 uint64_t addr(const void *p) { return reinterpret_cast<uint64_t>(p); }
 
 int grow(DevBuf &b, size_t bytes) {
@@ -59,20 +59,7 @@ int grow(DevBuf &b, size_t bytes) {
 int check_handle(const CipherCore *g) { return g ? 0 : rc_fail(RC_ERR_ARGUMENT, "null cipher"); }
 
 int acquire(CipherCore *g, Workspace *&out) {
-    Workspace &w = g->ws[g->next_ws++ & 1];
-    if (w.pending) {  // its previous call must have consumed the staging
-        GCM_DBG("wait for workspace %u", (g->next_ws - 1) & 1);
-        RC_HIP_TRY(hipEventSynchronize(w.done));
-        w.pending = false;
-    }
-    out = &w;
-    return 0;
-}
-
-int finish(Workspace &w, hipStream_t st) {
-    RC_HIP_TRY(hipEventRecord(w.done, st));
-    w.pending = true;
-    return 0;
+    return g->ring.acquire(out, [](unsigned slot) { GCM_DBG("wait for workspace %u", slot); });
 }
 
 // n host-built items, longest first (the kernel hands them out in list order)
@@ -91,11 +78,9 @@ int enqueue_items(CipherCore *g, int mode, std::vector<GcmItem> &items, uint8_t 
     std::memcpy(h + 16, items.data(), n * sizeof(GcmItem));
     RC_HIP_TRY(hipMemcpyAsync(w->d_stage.p, h, bytes, hipMemcpyHostToDevice, st));
     const GcmItem *d_items = reinterpret_cast<const GcmItem *>(static_cast<uint8_t *>(w->d_stage.p) + 16);
-    rc::PairTimer::Pair ev{};
-    if (int rc = g->timer.begin(st, ev)) return rc;
-    if (int rc = g->desc.launch(g, mode, d_items, nullptr, n, d_ok, st)) return rc;
-    if (int rc = g->timer.end(st, ev)) return rc;
-    return finish(*w, st);
+    if (int rc = rc::timed(g->timer, st, [&] { return g->desc.launch(g, mode, d_items, nullptr, n, d_ok, st); }))
+        return rc;
+    return g->ring.finish(*w, st);
 }
 
 }  // namespace
@@ -112,21 +97,14 @@ int core_check_device(int device) {
         char err[256];
         if (rc::read_knobs(knobs, err, sizeof err)) return rc_fail(RC_ERR_ARGUMENT, "%s", err);
     }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
-        return rc_fail(RC_ERR_NO_DEVICE, "no HIP device %d", device);
-    return 0;
+    return rc::check_device(device);
 }
 
 int core_create(CipherCore *g, int device, int (*setup)(CipherCore *), void (*destroy)(void *)) {
     DeviceGuard guard(device);
     g->device = device;
-    auto events = [g]() -> int {
-        for (auto &w : g->ws) RC_HIP_TRY(hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
-        return 0;
-    };
     int rc = setup ? setup(g) : 0;
-    if (!rc) rc = events();
+    if (!rc) rc = g->ring.create();
     if (rc) {
         destroy(g);
         return rc;
@@ -136,25 +114,19 @@ int core_create(CipherCore *g, int device, int (*setup)(CipherCore *), void (*de
 }
 
 void core_destroy(CipherCore *g, void (*release_own)(CipherCore *)) {
-    rc_untrack(g);
-    // a call still running on another thread (a daemon thread when the exit hook runs)
-    // finishes first: its buffers and streams go only after it
-    std::lock_guard<std::mutex> lock(g->mu);
-    DeviceGuard guard(g->device);
-    (void)hipDeviceSynchronize();
-    if (release_own) release_own(g);
-    for (auto &w : g->ws) {
-        w.h_stage.release();
-        w.d_stage.release();
-        if (w.done) (void)hipEventDestroy(w.done);
-        w.done = nullptr;
-    }
-    g->h_in.release();
-    g->h_out.release();
-    g->d_in.release();
-    g->d_out.release();
-    g->d_ok.release();
-    g->timer.release();
+    rc::teardown(g, [g, release_own] {
+        if (release_own) release_own(g);
+        g->ring.release([](CipherCore::Staging &w) {
+            w.h_stage.release();
+            w.d_stage.release();
+        });
+        g->h_in.release();
+        g->h_out.release();
+        g->d_in.release();
+        g->d_out.release();
+        g->d_ok.release();
+        g->timer.release();
+    });
 }
 
 int encrypt_device(CipherCore *g, uint64_t n, const uint8_t *const *d_in, const uint64_t *lens,
@@ -205,14 +177,8 @@ int run_host(CipherCore *g, int mode, uint64_t n, const uint8_t *const *in, cons
     const CipherDesc &c = g->desc;
     const bool dec = mode == kDecrypt;
     const char *what = dec ? "decrypt" : mode == kEncrypt ? "encrypt" : "raw";
-    std::vector<uint64_t> in_off(n), out_off(n);
-    uint64_t a = 0, b = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        in_off[i] = a;
-        a += up16(lens[i]);
-        out_off[i] = b;
-        b += up16(out_lens[i]);
-    }
+    std::vector<uint64_t> in_off, out_off;
+    const uint64_t a = rc::offsets16(n, lens, in_off), b = rc::offsets16(n, out_lens, out_off);
     const uint64_t key_off = a, nonce_off = a + uint64_t(c.key_slot) * n;
     const uint64_t in_total = nonce_off + (nonces ? uint64_t(c.nonce_slot) * n : 0);
     const uint64_t out_room = dec ? b + 16 : b;  // (every plaintext may be empty)
@@ -346,11 +312,6 @@ int encrypt_chunks(CipherCore *g, const rc_chunker *layout, uint64_t n,
     const uint64_t *du = reinterpret_cast<const uint64_t *>(d + 16);
     uint64_t *chunk_off = reinterpret_cast<uint64_t *>(d + up);
     GcmItem *items = reinterpret_cast<GcmItem *>(d + items_off);
-    rc::PairTimer::Pair ev{};
-    if (int rc = g->timer.begin(st, ev)) return rc;
-    // chunk_off = the exclusive scan of max(count, 0): a stream whose count is negative
-    // (RC_COUNT_OVERFLOW, RC_COUNT_FAULT) contributes no item, and the kernel takes k < total
-    if (rc_b2_launch_scan(d_counts, n, chunk_off, st)) return rc_fail(RC_ERR_HIP, "%s", rc_b2_launch_error());
     GcmChunkLists c{};
     c.ptrs = du;
     c.cut_base = du + n;
@@ -364,10 +325,15 @@ int encrypt_chunks(CipherCore *g, const rc_chunker *layout, uint64_t n,
     c.nonces = addr(d_nonces);
     c.out = addr(d_out);
     c.nonce_bytes = g->desc.nonce_bytes;
-    if (rc_gcm_launch_chunk_items(c, items, st)) return rc_fail(RC_ERR_HIP, "%s", rc_gcm_launch_error());
-    if (int rc = g->desc.launch(g, kEncrypt, items, chunk_off + n, total_cap, nullptr, st)) return rc;
-    if (int rc = g->timer.end(st, ev)) return rc;
-    return finish(*w, st);
+    if (int rc = rc::timed(g->timer, st, [&] {
+            // chunk_off = the exclusive scan of max(count, 0): a stream whose count is negative
+            // (RC_COUNT_OVERFLOW, RC_COUNT_FAULT) contributes no item, and the kernel takes k < total
+            if (int rc = rc_b2_launch_scan(d_counts, n, chunk_off, st)) return rc;
+            if (int rc = rc_gcm_launch_chunk_items(c, items, st)) return rc;
+            return g->desc.launch(g, kEncrypt, items, chunk_off + n, total_cap, nullptr, st);
+        }))
+        return rc;
+    return g->ring.finish(*w, st);
 }
 
 int encrypt_chunks_select(CipherCore *g, const rc_chunker *layout, uint64_t n,
@@ -416,8 +382,6 @@ int encrypt_chunks_select(CipherCore *g, const rc_chunker *layout, uint64_t n,
     const uint64_t *du = reinterpret_cast<const uint64_t *>(d + 16);
     uint64_t *tile_sums = reinterpret_cast<uint64_t *>(d + up);
     GcmItem *items = reinterpret_cast<GcmItem *>(d + items_off);
-    rc::PairTimer::Pair ev{};
-    if (int rc = g->timer.begin(st, ev)) return rc;
     GcmSelectLists c{};
     c.ptrs = du;
     c.cut_base = du + n;
@@ -430,26 +394,24 @@ int encrypt_chunks_select(CipherCore *g, const rc_chunker *layout, uint64_t n,
     c.nonces = addr(d_nonces);
     c.out = addr(d_out);
     c.nonce_bytes = g->desc.nonce_bytes;
-    // the work list holds d_totals[1] items (the selected chunks, on the device); the cipher
-    // kernel takes k < that over the bound total_cap, as on the unfiltered path
-    if (rc_gcm_launch_select_items(c, tile_sums, d_blob_off, d_totals, items, st))
-        return rc_fail(RC_ERR_HIP, "%s", rc_gcm_launch_error());
-    if (int rc = g->desc.launch(g, kEncrypt, items, d_totals + 1, total_cap, nullptr, st)) return rc;
-    if (int rc = g->timer.end(st, ev)) return rc;
-    return finish(*w, st);
+    if (int rc = rc::timed(g->timer, st, [&] {
+            // the work list holds d_totals[1] items (the selected chunks, on the device); the cipher
+            // kernel takes k < that over the bound total_cap, as on the unfiltered path
+            if (int rc = rc_gcm_launch_select_items(c, tile_sums, d_blob_off, d_totals, items, st)) return rc;
+            return g->desc.launch(g, kEncrypt, items, d_totals + 1, total_cap, nullptr, st);
+        }))
+        return rc;
+    return g->ring.finish(*w, st);
 }
 
 int timing_enable(CipherCore *g, int enable) {
     if (int rc = check_handle(g)) return rc;
-    g->timer.enabled = enable != 0;
-    return RC_OK;
+    return rc::timing_enable(g, {&g->timer}, enable);
 }
 
 int timing_read(CipherCore *g, double *ms, uint64_t *calls) {
     if (int rc = check_handle(g)) return rc;
-    std::lock_guard<std::mutex> lock(g->mu);
-    DeviceGuard guard(g->device);
-    return g->timer.read(ms, calls);
+    return rc::timing_read(g, g->timer, ms, calls);
 }
 
 }  // namespace rc_cipher

@@ -63,13 +63,11 @@ struct CipherCore {
     CipherDesc desc;
     int device = 0;
     std::mutex mu;
-    struct Workspace {
+    struct Staging {
         StagingBuf h_stage;  // [header 16 B] [host-built staging]
         DevBuf d_stage;      // its device copy (+ device-built lists)
-        hipEvent_t done = nullptr;
-        bool pending = false;
-    } ws[2];
-    unsigned next_ws = 0;
+    };
+    rc::SlotRing<Staging> ring;
     // blocking host paths
     StagingBuf h_in, h_out;
     DevBuf d_in, d_out, d_ok;

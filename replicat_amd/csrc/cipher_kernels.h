@@ -25,7 +25,6 @@ struct GcmArgs {
 
 constexpr int kGcmThreads = 1024;  // 16 waves: one workgroup per CU (153 KiB of LDS)
 
-const char *rc_gcm_launch_error(void);
 
 // AES-GCM over a work list (key_bytes 16 / 24 / 32): workgroup i takes item i; groups = the item
 // count (or, with d_total, its bound).

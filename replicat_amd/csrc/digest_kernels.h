@@ -25,7 +25,6 @@ constexpr uint64_t kB2LaneGroups = 1024;     // lane-only launches: four waves p
 constexpr int kB2Buckets = 256;       // length classes of the longest-first work list
 constexpr uint64_t kB2Slot = 64;      // bytes per digest slot (BLAKE2b's largest digest)
 
-const char *rc_b2_launch_error(void);
 
 // Digests of n items (host-built work list, already on the device).
 // lane_max: items of at most this many bytes are hashed one per lane, longer ones by quads

@@ -18,9 +18,8 @@
 // lane, which keeps the kernels free of a prepared midstate at 1,900 VALU instructions each.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-
 #include "blake2b_lane.h"
+#include "capi_internal.h"
 #include "gc_kernels.h"
 #include "index_lookup.h"
 
@@ -194,26 +193,13 @@ __global__ __launch_bounds__(kGcThreads) void rc_gc_scatter_kernel(const uint8_t
     out[pos] = index_base + uint64_t(blockIdx.x) * kGcThreads + threadIdx.x;
 }
 
-namespace {
-thread_local char g_gc_err[256];
-
-int gc_status(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(g_gc_err, sizeof g_gc_err, "%s: %s", what, hipGetErrorString(e));
-    return 1;
-}
-}  // namespace
-
-const char *rc_gc_launch_error(void) { return g_gc_err; }
-
 int rc_gc_launch_names(const rc_blake2b_state *d_mac, uint64_t n, const uint8_t *d_in,
                        uint32_t in_bytes, bool hash_input, const uint64_t *d_sel, uint64_t sel_base,
                        uint8_t *d_names, uint8_t *d_tags, hipStream_t st) {
     if (!n) return 0;
     rc_gc_names_kernel<<<static_cast<unsigned>(rc_gc_groups(n)), kGcThreads, 0, st>>>(
         d_mac, n, d_in, in_bytes, hash_input ? 1 : 0, d_sel, sel_base, d_names, d_tags);
-    return gc_status("rc_gc_names_kernel");
+    return rc::launch_status("rc_gc_names_kernel");
 }
 
 int rc_gc_launch_sweep(const IndexView &v, const rc_blake2b_state *d_mac, uint64_t n,
@@ -222,7 +208,7 @@ int rc_gc_launch_sweep(const IndexView &v, const rc_blake2b_state *d_mac, uint64
     if (!n) return 0;
     rc_gc_sweep_kernel<<<static_cast<unsigned>(rc_gc_groups(n)), kGcThreads, 0, st>>>(
         v, d_mac, n, d_names, d_tags, d_verdict);
-    return gc_status("rc_gc_sweep_kernel");
+    return rc::launch_status("rc_gc_sweep_kernel");
 }
 
 int rc_gc_launch_compact(const uint8_t *d_flags, uint64_t n, uint8_t want, uint64_t index_base,
@@ -230,13 +216,13 @@ int rc_gc_launch_compact(const uint8_t *d_flags, uint64_t n, uint8_t want, uint6
     const unsigned groups = static_cast<unsigned>(rc_gc_groups(n));
     if (groups) {
         rc_gc_count_kernel<<<groups, kGcThreads, 0, st>>>(d_flags, n, want, d_scratch);
-        if (gc_status("rc_gc_count_kernel")) return 1;
+        if (int rc = rc::launch_status("rc_gc_count_kernel")) return rc;
     }
     rc_gc_scan_kernel<<<1, 1024, 0, st>>>(d_scratch, groups, d_total);
-    if (gc_status("rc_gc_scan_kernel")) return 1;
+    if (int rc = rc::launch_status("rc_gc_scan_kernel")) return rc;
     if (groups) {
         rc_gc_scatter_kernel<<<groups, kGcThreads, 0, st>>>(d_flags, n, want, d_scratch, index_base, d_out);
-        if (gc_status("rc_gc_scatter_kernel")) return 1;
+        if (int rc = rc::launch_status("rc_gc_scatter_kernel")) return rc;
     }
     return 0;
 }

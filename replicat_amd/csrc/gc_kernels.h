@@ -11,7 +11,6 @@ constexpr int kGcThreads = 256;  // one lane per item; 4 waves per workgroup
 // What a sweep lane may write (include/replicat_gc.h: RC_GC_*).
 constexpr uint8_t kGcReferenced = 0, kGcDelete = 1, kGcTagMismatch = 2, kGcExhausted = 3;
 
-const char *rc_gc_launch_error(void);
 
 // Workgroups of a launch over n items, and the words of scratch the compaction of n flags takes
 // (one count per workgroup and the total).

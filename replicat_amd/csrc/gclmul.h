@@ -182,5 +182,4 @@ int rc_launch_fill_streams(uint8_t *d_dst, uint64_t n, uint64_t nbytes, uint64_t
 // block: 0 = the tile kernel's schedule `sched`, else interleaved static runs of `block` tiles
 int rc_launch_read_probe(const uint8_t *d_src, uint64_t nbytes, uint32_t *d_out, uint32_t block,
                          rc::TileSched sched, void *stream);
-const char *rc_launch_error(void);
 }

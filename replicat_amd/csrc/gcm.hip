@@ -37,6 +37,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "capi_internal.h"
 #include "cipher_kernels.h"
 
 #ifdef RC_GCM_TRACE  // diagnostic build (scripts/gcm_diag.cpp): progress word of workgroup 0
@@ -572,26 +573,15 @@ __global__ __launch_bounds__(kSelectThreads) void rc_gcm_select_items_kernel(Gcm
 }
 
 namespace {
-thread_local char g_gcm_err[256];
-
-int gcm_status(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(g_gcm_err, sizeof g_gcm_err, "%s: %s", what, hipGetErrorString(e));
-    return 1;
-}
-
 template <int NR>
 int launch_nr(bool decrypt, const GcmArgs &args, unsigned groups, hipStream_t stream) {
     if (decrypt)
         rc_gcm_kernel<NR, true><<<groups, kGcmThreads, 0, stream>>>(args);
     else
         rc_gcm_kernel<NR, false><<<groups, kGcmThreads, 0, stream>>>(args);
-    return gcm_status("rc_gcm_kernel");
+    return rc::launch_status("rc_gcm_kernel");
 }
 }  // namespace
-
-const char *rc_gcm_launch_error(void) { return g_gcm_err; }
 
 #ifdef RC_GCM_TRACE
 int rc_gcm_trace_read(unsigned long long *out, hipStream_t st) {
@@ -613,9 +603,7 @@ int rc_gcm_launch(uint32_t key_bytes, bool decrypt, const GcmArgs &args, unsigne
         case 16: return launch_nr<10>(decrypt, args, groups, stream);
         case 24: return launch_nr<12>(decrypt, args, groups, stream);
         case 32: return launch_nr<14>(decrypt, args, groups, stream);
-        default:
-            snprintf(g_gcm_err, sizeof g_gcm_err, "bad AES key size %u", key_bytes);
-            return 1;
+        default: return rc_fail(RC_ERR_HIP, "bad AES key size %u", key_bytes);
     }
 }
 
@@ -623,7 +611,7 @@ int rc_gcm_launch_chunk_items(const GcmChunkLists &c, GcmItem *items, hipStream_
     if (!c.n) return 0;
     const unsigned groups = static_cast<unsigned>((c.n + c.spw - 1) / c.spw);
     rc_gcm_items_kernel<<<groups, 256, 0, stream>>>(c, items);
-    return gcm_status("rc_gcm_items_kernel");
+    return rc::launch_status("rc_gcm_items_kernel");
 }
 
 int rc_gcm_launch_select_items(const GcmSelectLists &c, uint64_t *tile_sums, uint64_t *blob_off,
@@ -631,7 +619,7 @@ int rc_gcm_launch_select_items(const GcmSelectLists &c, uint64_t *tile_sums, uin
     if (!c.n || !c.slots) return 0;
     const unsigned tiles = static_cast<unsigned>(rc_gcm_select_tiles(c.slots));
     rc_gcm_select_scan_kernel<<<tiles, kSelectThreads, 0, stream>>>(c, tile_sums);
-    if (gcm_status("rc_gcm_select_scan_kernel")) return 1;
+    if (int rc = rc::launch_status("rc_gcm_select_scan_kernel")) return rc;
     rc_gcm_select_items_kernel<<<tiles, kSelectThreads, 0, stream>>>(c, tile_sums, blob_off, totals, items);
-    return gcm_status("rc_gcm_select_items_kernel");
+    return rc::launch_status("rc_gcm_select_items_kernel");
 }

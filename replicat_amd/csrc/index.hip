@@ -11,8 +11,7 @@
 // was written before the launch.  Every probe loop is bounded by the table size.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-
+#include "capi_internal.h"
 #include "index_kernels.h"
 #include "index_lookup.h"
 
@@ -134,49 +133,38 @@ __global__ __launch_bounds__(kIndexThreads) void rc_index_reinsert_kernel(IndexV
 }
 
 namespace {
-thread_local char g_index_err[256];
-
-int index_status(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(g_index_err, sizeof g_index_err, "%s: %s", what, hipGetErrorString(e));
-    return 1;
-}
-
 unsigned groups_for(uint64_t lanes) { return static_cast<unsigned>((lanes + kIndexThreads - 1) / kIndexThreads); }
 }  // namespace
-
-const char *rc_index_launch_error(void) { return g_index_err; }
 
 int rc_index_launch_stage(const IndexView &v, const IndexWork &w, const uint8_t *names, hipStream_t st) {
     if (!w.slots) return 0;
     rc_index_stage_kernel<<<groups_for(w.slots), kIndexThreads, 0, st>>>(v, w, names);
-    return index_status("rc_index_stage_kernel");
+    return rc::launch_status("rc_index_stage_kernel");
 }
 
 int rc_index_launch_insert(const IndexView &v, const IndexWork &w, hipStream_t st) {
     if (!w.slots) return 0;
     rc_index_insert_kernel<<<groups_for(w.slots), kIndexThreads, 0, st>>>(v, w);
-    return index_status("rc_index_insert_kernel");
+    return rc::launch_status("rc_index_insert_kernel");
 }
 
 int rc_index_launch_resolve(const IndexView &v, const IndexWork &w, int64_t *owner, uint8_t *fresh,
                             hipStream_t st) {
     if (!w.slots) return 0;
     rc_index_resolve_kernel<<<groups_for(w.slots), kIndexThreads, 0, st>>>(v, w, owner, fresh);
-    return index_status("rc_index_resolve_kernel");
+    return rc::launch_status("rc_index_resolve_kernel");
 }
 
 int rc_index_launch_lookup(const IndexView &v, uint64_t n, const uint8_t *names, int64_t *owner,
                            hipStream_t st) {
     if (!n) return 0;
     rc_index_lookup_kernel<<<groups_for(n), kIndexThreads, 0, st>>>(v, n, names, owner);
-    return index_status("rc_index_lookup_kernel");
+    return rc::launch_status("rc_index_lookup_kernel");
 }
 
 int rc_index_launch_reinsert(const IndexView &v, const uint64_t *old_table, uint64_t old_entries,
                              hipStream_t st) {
     if (!old_entries) return 0;
     rc_index_reinsert_kernel<<<groups_for(old_entries), kIndexThreads, 0, st>>>(v, old_table, old_entries);
-    return index_status("rc_index_reinsert_kernel");
+    return rc::launch_status("rc_index_reinsert_kernel");
 }

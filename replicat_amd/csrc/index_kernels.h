@@ -25,7 +25,6 @@ struct IndexWork {
     uint64_t n, slots, id_base;
 };
 
-const char *rc_index_launch_error(void);
 
 // An index's view for a launch of another module's (gc.hip's sweep reads the table and the pool).
 // The caller orders that launch against the index's other calls as it would order those.

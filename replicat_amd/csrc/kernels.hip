@@ -29,14 +29,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "capi_internal.h"
 #include "gclmul.h"
 #include "diag.h"
 
 using namespace rc;
 
 namespace {
-
-thread_local char g_launch_err[256];
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // Stream bytes are global memory; the pointers come out of descriptor arrays, so say so
@@ -2639,13 +2638,6 @@ __global__ void rc_fill_streams_kernel(uint8_t *__restrict__ dst, uint64_t n, ui
     }
 }
 
-int launch_status(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(g_launch_err, sizeof g_launch_err, "%s: %s", what, hipGetErrorString(e));
-    return 1;
-}
-
 int cu_count() {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 256;
@@ -2659,8 +2651,6 @@ int cu_count() {
 
 extern "C" {
 
-const char *rc_launch_error(void) { return g_launch_err; }
-
 int rc_launch_tiles(const KeyTables *d_tables, StreamDesc desc, uint64_t n_streams,
                     uint64_t n_tiles, TileRecord *d_records, GroupRecord *d_grp,
                     uint32_t hot, uint32_t *d_xlist, uint32_t *d_ctr, uint64_t epoch,
@@ -2673,14 +2663,13 @@ int rc_launch_tiles(const KeyTables *d_tables, StreamDesc desc, uint64_t n_strea
         if (est == st) return 0;
         // `tiled` may be mid_event itself, already recorded after the tile kernel
         if ((tiled != mid_event && hipEventRecord((hipEvent_t)tiled, st) != hipSuccess) ||
-            hipStreamWaitEvent(est, (hipEvent_t)tiled, 0) != hipSuccess) {
-            snprintf(g_launch_err, sizeof g_launch_err, "edge stream hand-over failed");
-            return 1;
-        }
+            hipStreamWaitEvent(est, (hipEvent_t)tiled, 0) != hipSuccess)
+            return rc_fail(RC_ERR_HIP, "edge stream hand-over failed");
         return 0;
     };
     if (n_tiles == 0) {
-        if (mid_event && hipEventRecord((hipEvent_t)mid_event, st) != hipSuccess) return 1;
+        if (mid_event && hipEventRecord((hipEvent_t)mid_event, st) != hipSuccess)
+            return rc_fail(RC_ERR_HIP, "hipEventRecord failed");
         return hand_over();
     }
     const uint64_t waves_per_wg = 1024 / kWaveSize;
@@ -2711,12 +2700,10 @@ int rc_launch_tiles(const KeyTables *d_tables, StreamDesc desc, uint64_t n_strea
         hipLaunchKernelGGL((rc_tile_kernel<1, false>), dim3((unsigned)grid), dim3(1024), 0, st,
                            d_tables, desc, n_streams, U, d_records, d_grp, hot, d_xlist, d_xcount,
                            d_ctr);
-    if (launch_status("rc_tile_kernel")) return 1;
-    if (mid_event && hipEventRecord((hipEvent_t)mid_event, st) != hipSuccess) {
-        snprintf(g_launch_err, sizeof g_launch_err, "hipEventRecord failed");
-        return 1;
-    }
-    if (hand_over()) return 1;
+    if (int rc = launch_status("rc_tile_kernel")) return rc;
+    if (mid_event && hipEventRecord((hipEvent_t)mid_event, st) != hipSuccess)
+        return rc_fail(RC_ERR_HIP, "hipEventRecord failed");
+    if (int rc = hand_over()) return rc;
     // one wave per tie list (almost always empty) and per host-listed tile, grid-strided
     uint64_t egrid = (U.n_units + 3) / 4;
     if (egrid > 4 * cus) egrid = 4 * cus;
@@ -2784,7 +2771,7 @@ int rc_launch_chain(const KeyTables *d_tables, StreamDesc desc, uint64_t n_strea
         hipLaunchKernelGGL((rc_spec_kernel<kRecUnroll, false>), dim3((unsigned)grid),
                            dim3(kChainWaves * kWaveSize), 0, st, d_tables, desc, n_streams, prm,
                            n_segs, d_records, d_cuts, d_counts, d_scratch, d_seg_counts, seg_rcount);
-    if (launch_status("rc_spec_kernel")) return 1;
+    if (int rc = launch_status("rc_spec_kernel")) return rc;
     if (!any_multi) return 0;
     const uint64_t sgrid = (n_segs + 3) / 4, jgrid = (n_streams + kChainWaves - 1) / kChainWaves;
     if (!(join & RC_JOIN_WALK_ONLY)) {
@@ -2797,21 +2784,21 @@ int rc_launch_chain(const KeyTables *d_tables, StreamDesc desc, uint64_t n_strea
             hipLaunchKernelGGL(rc_merge_kernel<kRecUnroll>, dim3((unsigned)sgrid), dim3(256), 0,
                                st, d_tables, desc, n_streams, prm, n_segs, d_records, d_scratch,
                                (const uint64_t *)d_seg_counts, seg_merge, seg_rcount, repair);
-        if (launch_status("rc_merge_kernel")) return 1;
+        if (int rc = launch_status("rc_merge_kernel")) return rc;
         hipLaunchKernelGGL(rc_scan_kernel, dim3((unsigned)jgrid), dim3(kChainWaves * kWaveSize), 0,
                            st, desc, n_streams, prm, (const uint64_t *)d_seg_counts,
                            (const uint64_t *)seg_merge, (const uint64_t *)seg_rcount, seg_off,
                            seg_slice, d_counts);
-        if (launch_status("rc_scan_kernel")) return 1;
+        if (int rc = launch_status("rc_scan_kernel")) return rc;
         hipLaunchKernelGGL(rc_copy_kernel, dim3((unsigned)sgrid), dim3(256), 0, st, desc,
                            n_streams, prm, n_segs, (const uint64_t *)d_scratch,
                            (const uint64_t *)seg_off, (const uint64_t *)seg_slice, d_cuts,
                            (const int64_t *)d_counts);
-        if (launch_status("rc_copy_kernel")) return 1;
+        if (int rc = launch_status("rc_copy_kernel")) return rc;
     } else {
         hipLaunchKernelGGL(rc_mark_kernel, dim3((unsigned)jgrid), dim3(kChainWaves * kWaveSize), 0,
                            st, desc, n_streams, prm, d_counts);
-        if (launch_status("rc_mark_kernel")) return 1;
+        if (int rc = launch_status("rc_mark_kernel")) return rc;
     }
     if (small)
         hipLaunchKernelGGL(rc_join_kernel<1>, dim3((unsigned)jgrid), dim3(kChainWaves * kWaveSize),
@@ -2836,10 +2823,8 @@ int rc_launch_read_probe(const uint8_t *d_src, uint64_t nbytes, uint32_t *d_out,
     // kernel's schedule `sched` (d_out[1] is the grab counter)
     const TileUnits U = tile_units(n_tiles, grid * (1024 / kWaveSize), sched);
     if (block == 0 && U.n_units > U.nw &&
-        hipMemsetAsync(d_out + 1, 0, sizeof(uint32_t), (hipStream_t)stream) != hipSuccess) {
-        snprintf(g_launch_err, sizeof g_launch_err, "hipMemsetAsync failed");
-        return 1;
-    }
+        hipMemsetAsync(d_out + 1, 0, sizeof(uint32_t), (hipStream_t)stream) != hipSuccess)
+        return rc_fail(RC_ERR_HIP, "hipMemsetAsync failed");
     if (U.n_groups)
         hipLaunchKernelGGL(rc_read_probe_kernel<true>, dim3((unsigned)grid), dim3(1024), 0,
                            (hipStream_t)stream, d_src, n_tiles, d_out, (uint64_t)block, U, d_out + 1);

@@ -17,8 +17,7 @@
 // case, so one wave per buffer is enough: ~1 KiB per store step, a 5 MB chunk in ~5000 steps.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-
+#include "capi_internal.h"
 #include "restore_kernels.h"
 
 namespace {
@@ -64,23 +63,11 @@ __global__ __launch_bounds__(kRestoreThreads) void rc_restore_verdict_kernel(Res
     }
 }
 
-namespace {
-thread_local char g_restore_err[256];
-}
-
-const char *rc_restore_launch_error(void) { return g_restore_err; }
-
 int rc_restore_launch_verdict(const RestoreVerdictArgs &a, hipStream_t stream) {
     if (!a.n) return 0;
     const uint64_t per = kRestoreThreads / kWave;
     const uint64_t groups = (a.n + per - 1) / per;
-    if (groups > 0x7FFFFFFFull) {
-        snprintf(g_restore_err, sizeof g_restore_err, "%llu chunks in one call", (unsigned long long)a.n);
-        return 1;
-    }
+    if (groups > 0x7FFFFFFFull) return rc_fail(RC_ERR_HIP, "%llu chunks in one call", (unsigned long long)a.n);
     rc_restore_verdict_kernel<<<static_cast<unsigned>(groups), kRestoreThreads, 0, stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(g_restore_err, sizeof g_restore_err, "rc_restore_verdict_kernel: %s", hipGetErrorString(e));
-    return 1;
+    return rc::launch_status("rc_restore_verdict_kernel");
 }

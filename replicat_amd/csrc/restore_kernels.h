@@ -22,7 +22,6 @@ struct RestoreVerdictArgs {
 
 constexpr int kRestoreThreads = 256;  // 4 waves: one wave per chunk
 
-const char *rc_restore_launch_error(void);
 
 // status[i] for n chunks, and zeros over plain[i] where it is not RC_CHUNK_OK.
 int rc_restore_launch_verdict(const RestoreVerdictArgs &a, hipStream_t stream);

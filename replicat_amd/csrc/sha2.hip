@@ -439,13 +439,13 @@ int rc_sha2_launch_items(const B2Item *d_items, const uint64_t *d_total, uint64_
         else
             rc_sha512_split_kernel<<<grid, kShaThreads, 0, stream>>>(d_items, d_total, n, outlen, d_out, lane_max,
                                                                      static_cast<uint32_t>(wb));
-        return rc_sha_status("rc_sha2_split_kernel");
+        return rc::launch_status("rc_sha2_split_kernel");
     }
     if (outlen <= 32)
         rc_sha256_kernel<<<rc_sha_grid(upper), kShaThreads, 0, stream>>>(d_items, d_total, n, outlen, d_out);
     else
         rc_sha512_kernel<<<rc_sha_grid(upper), kShaThreads, 0, stream>>>(d_items, d_total, n, outlen, d_out);
-    return rc_sha_status("rc_sha2_kernel");
+    return rc::launch_status("rc_sha2_kernel");
 }
 
 int rc_sha2_launch_update(const B2UItem *d_items, uint64_t n, uint32_t outlen, uint8_t *d_out,
@@ -455,7 +455,7 @@ int rc_sha2_launch_update(const B2UItem *d_items, uint64_t n, uint32_t outlen, u
         rc_sha256_update_kernel<<<rc_sha_grid(n), kShaThreads, 0, stream>>>(d_items, n, outlen, d_out);
     else
         rc_sha512_update_kernel<<<rc_sha_grid(n), kShaThreads, 0, stream>>>(d_items, n, outlen, d_out);
-    return rc_sha_status("rc_sha2_update_kernel");
+    return rc::launch_status("rc_sha2_update_kernel");
 }
 
 // The digest_size and algo words of every item's state record (the same offsets in all three
@@ -472,5 +472,5 @@ __global__ __launch_bounds__(256) void rc_sha_tags_kernel(const B2UItem *__restr
 int rc_sha_launch_tags(const B2UItem *d_items, uint64_t n, uint32_t *d_tags, hipStream_t stream) {
     if (!n) return 0;
     rc_sha_tags_kernel<<<static_cast<unsigned>((n + 255) / 256), 256, 0, stream>>>(d_items, n, d_tags);
-    return rc_sha_status("rc_sha_tags_kernel");
+    return rc::launch_status("rc_sha_tags_kernel");
 }

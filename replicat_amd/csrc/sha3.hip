@@ -352,7 +352,7 @@ int rc_sha3_launch_items(const B2Item *d_items, const uint64_t *d_total, uint64_
         case 48: launch_split<104>(d_items, d_total, n, upper, outlen, d_out, lane_max, stream); break;
         default: launch_split<72>(d_items, d_total, n, upper, outlen, d_out, lane_max, stream); break;
         }
-        return rc_sha_status("rc_sha3_split_kernel");
+        return rc::launch_status("rc_sha3_split_kernel");
     }
     const unsigned grid = rc_sha_grid(upper);
     switch (outlen) {
@@ -361,7 +361,7 @@ int rc_sha3_launch_items(const B2Item *d_items, const uint64_t *d_total, uint64_
     case 48: rc_sha3_kernel<104><<<grid, kShaThreads, 0, stream>>>(d_items, d_total, n, outlen, d_out); break;
     default: rc_sha3_kernel<72><<<grid, kShaThreads, 0, stream>>>(d_items, d_total, n, outlen, d_out); break;
     }
-    return rc_sha_status("rc_sha3_kernel");
+    return rc::launch_status("rc_sha3_kernel");
 }
 
 int rc_sha3_launch_update(const B2UItem *d_items, uint64_t n, uint32_t outlen, uint8_t *d_out,
@@ -374,5 +374,5 @@ int rc_sha3_launch_update(const B2UItem *d_items, uint64_t n, uint32_t outlen, u
     case 48: rc_sha3_update_kernel<104><<<grid, kShaThreads, 0, stream>>>(d_items, n, outlen, d_out); break;
     default: rc_sha3_update_kernel<72><<<grid, kShaThreads, 0, stream>>>(d_items, n, outlen, d_out); break;
     }
-    return rc_sha_status("rc_sha3_update_kernel");
+    return rc::launch_status("rc_sha3_update_kernel");
 }

@@ -5,8 +5,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 
+#include "capi_internal.h"
 #include "digest_kernels.h"
 
 constexpr int kShaThreads = 256;           // one message per lane, 4 waves per workgroup
@@ -17,14 +17,6 @@ constexpr uint64_t kShaAllLanes = ~0ull;   // lane_max: every item one per lane 
 static_assert(sizeof(rc_sha2_state) == 256 && sizeof(rc_sha3_state) == 256,
               "every hash state is a 256-byte device record");
 
-inline thread_local char g_sha_err[256];
-inline const char *rc_sha_launch_error(void) { return g_sha_err; }
-inline int rc_sha_status(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(g_sha_err, sizeof g_sha_err, "%s: %s", what, hipGetErrorString(e));
-    return 1;
-}
 inline unsigned rc_sha_grid(uint64_t upper) {
     uint64_t wg = (upper + kShaThreads - 1) / kShaThreads;
     if (wg > kShaMaxGroups) wg = kShaMaxGroups;

@@ -58,6 +58,80 @@ CHILD = textwrap.dedent("""
 """)
 
 
+# The families CHILD leaves out, each a raw handle with one tiny call still queued: three messages
+# of 0, 17 and 200 bytes through the cipher and the restore handle (which points at a leaked hasher
+# and a leaked rc_gcm, so the hook has to destroy it before them), 8 names, 8 listed entries.
+CHILD_FAMILIES = textwrap.dedent("""
+    import ctypes, sys
+    sys.path.insert(0, {root!r})
+    import numpy as np
+    import torch
+    from replicat_amd import _lib
+    torch.cuda.set_device(0)
+    torch.cuda.set_stream(torch.cuda.Stream())
+    hs = torch.cuda.current_stream().cuda_stream
+    L = _lib.lib()
+    u64 = lambda v: np.asarray(v, dtype=np.uint64)
+    rnd = lambda n: torch.randint(0, 256, (max(n, 1),), dtype=torch.uint8, device='cuda')
+    lens = [0, 17, 200]
+    lens_a = u64(lens)
+    keep = []
+
+    def buffers(sizes):
+        ts = [rnd(n) for n in sizes]
+        keep.extend(ts)
+        return u64([t.data_ptr() for t in ts])
+
+    def create(fn, *args):
+        h = ctypes.c_void_p()
+        assert fn(*args, ctypes.byref(h)) == 0, L.rc_last_error()
+        return h
+
+    cha = create(L.rc_chacha_create, 0)
+    ins, keys, nonces = buffers(lens), buffers([32] * 3), buffers([12] * 3)
+    outs = buffers([12 + n + 16 for n in lens])
+    assert L.rc_chacha_encrypt_device(cha, 3, ins.ctypes.data, lens_a.ctypes.data, keys.ctypes.data,
+                                      nonces.ctypes.data, outs.ctypes.data, hs) == 0, L.rc_last_error()
+
+    hasher = create(L.rc_blake2b_create, 64, 0)
+    gcm = create(L.rc_gcm_create, 256, 96, 0)
+    kdf = (ctypes.c_uint8 * 256)()
+    assert L.rc_blake2b_state_init(32, b'k' * 32, 32, None, 0, b'replicat', 8, kdf) == 0
+    restore = create(L.rc_restore_create, hasher, _lib.RC_CIPHER_AES_GCM, gcm, kdf)
+    over = L.rc_restore_overhead(restore)
+    assert over == 12 + 16
+    blob_lens = lens_a + over
+    blobs, plain = buffers(blob_lens.tolist()), buffers(lens)
+    expected, status = rnd(3 * 64), rnd(3)
+    assert L.rc_restore_verify_device(restore, 3, blobs.ctypes.data, blob_lens.ctypes.data,
+                                      expected.data_ptr(), plain.ctypes.data, status.data_ptr(),
+                                      hs) == 0, L.rc_last_error()
+
+    index = create(L.rc_index_create, 32, 64, 0)
+    names, owner, fresh = rnd(8 * 64), torch.zeros(8, dtype=torch.int64, device='cuda'), rnd(8)
+    base = ctypes.c_uint64()
+    assert L.rc_index_resolve_names_device(index, 8, names.data_ptr(), ctypes.byref(base),
+                                           owner.data_ptr(), fresh.data_ptr(), hs) == 0, L.rc_last_error()
+
+    gc = create(L.rc_gc_create, 32, 32, b'm' * 32, 32, 64, 0)
+    assert L.rc_gc_reference_host(gc, 4, bytes(range(128))) == 0, L.rc_last_error()
+    listed, tags, verdict = rnd(8 * 64), rnd(8 * 64), rnd(8)
+    delete_idx = torch.zeros(9, dtype=torch.int64, device='cuda')
+    assert L.rc_gc_sweep_device(gc, 8, listed.data_ptr(), tags.data_ptr(), 0, verdict.data_ptr(),
+                                delete_idx.data_ptr(), delete_idx.data_ptr() + 64, hs) == 0, L.rc_last_error()
+    keep += [expected, status, names, owner, fresh, listed, tags, verdict, delete_idx]
+    print('leaving with live handles', flush=True)
+""")
+
+
+@pytest.mark.gpu
+def test_exit_with_live_handles_of_every_other_family():
+    p = subprocess.run([sys.executable, '-c', CHILD_FAMILIES.format(root=ROOT)], capture_output=True,
+                       text=True, timeout=180)
+    assert 'leaving with live handles' in p.stdout, p.stderr[-3000:]
+    assert p.returncode == 0, (p.returncode, p.stderr[-3000:])
+
+
 @pytest.mark.gpu
 def test_exit_with_live_pipelined_handles():
     env = dict(os.environ, RC_PIPE_ALL='1')
