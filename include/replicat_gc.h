@@ -61,6 +61,12 @@ uint64_t rc_gc_capacity(const rc_gc *gc);
  * grows as needed, at least doubling.  Blocking. */
 int rc_gc_reference_host(rc_gc *gc, uint64_t n, const uint8_t *digests);
 
+/* The same for n digests already in DEVICE slots d_digests + 64 i (8-byte aligned; bytes past
+ * digest_bytes in a slot are ignored): the same batches and growth, without the host staging
+ * copy.  Work enqueued earlier on other streams that writes the slots must have been waited for
+ * by the caller or be ordered before the null stream.  Blocking. */
+int rc_gc_reference_device(rc_gc *gc, uint64_t n, const uint8_t *d_digests);
+
 /* clean, for n listed entries in DEVICE slots d_names + 64 i, d_tags + 64 i:
  *     d_verdict[i]    = RC_GC_* of entry i
  *     d_delete_idx[k] = index_base + i of the k-th entry with verdict RC_GC_DELETE, ascending

@@ -10,7 +10,8 @@ many device- or host-resident streams (``replicat_amd.chunker``).
 __version__ = '0.3.0'
 
 _GC_EXPORTS = ('GpuChunkGC', 'CleanPlan')
-__all__ = list(_GC_EXPORTS)
+_SNAPSHOTS_EXPORTS = ('GpuSnapshotLoader', 'LoadedSnapshot')
+__all__ = list(_GC_EXPORTS + _SNAPSHOTS_EXPORTS)
 
 
 def __getattr__(name):
@@ -19,4 +20,7 @@ def __getattr__(name):
     if name in _GC_EXPORTS:
         from . import gc
         return getattr(gc, name)
+    if name in _SNAPSHOTS_EXPORTS:  # snapshot loading (replicat_amd/snapshots.py), likewise
+        from . import snapshots
+        return getattr(snapshots, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -42,9 +42,10 @@ RC_DIGEST_SLOT = 64
 RC_HASH_BLAKE2B, RC_HASH_SHA2, RC_HASH_SHA3 = 0, 1, 2
 RC_CIPHER_NONE, RC_CIPHER_AES_GCM, RC_CIPHER_CHACHA20_POLY1305 = 0, 1, 2
 RC_CHUNK_OK, RC_CHUNK_BAD_TAG, RC_CHUNK_CORRUPT = 0, 1, 2
+RC_TABLE_OK, RC_TABLE_BAD_TAG, RC_TABLE_NOT_CANONICAL = 0, 1, 2
 
 # every symbol include/replicat_chunker.h, replicat_digest.h, replicat_cipher.h,
-# replicat_restore.h, replicat_index.h and replicat_gc.h declare:
+# replicat_restore.h, replicat_index.h, replicat_gc.h and replicat_snapshot.h declare:
 # name -> (restype, argtypes)
 _u64, _i64, _u32, _int, _p = ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p
 SIGNATURES = {
@@ -163,12 +164,26 @@ SIGNATURES = {
     'rc_gc_used': (_u64, [_p]),
     'rc_gc_capacity': (_u64, [_p]),
     'rc_gc_reference_host': (_int, [_p, _u64, _p]),
+    'rc_gc_reference_device': (_int, [_p, _u64, _p]),
     'rc_gc_sweep_device': (_int, [_p, _u64, _p, _p, _u64, _p, _p, _p, _p]),
     'rc_gc_sweep_host': (_int, [_p, _u64, _p, _p, _p, _p, ctypes.POINTER(_u64)]),
     'rc_gc_unreferenced_host': (_int, [_p, _u64, _p, _p, _p, _p, ctypes.POINTER(_u64)]),
     'rc_gc_timing_enable': (_int, [_p, _int]),
     'rc_gc_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
+    # replicat_snapshot.h
+    'rc_snapshot_create': (_int, [_u32, _int, _p, _p, _int, ctypes.POINTER(_p)]),
+    'rc_snapshot_destroy': (None, [_p]),
+    'rc_snapshot_stride': (_u32, [_p]),
+    'rc_snapshot_overhead': (_u32, [_p]),
+    'rc_snapshot_table_count': (_u64, [_p, _u64]),
+    'rc_snapshot_table_count_for': (_u64, [_u32, _u64]),
+    'rc_snapshot_tables_device': (_int, [_p, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'rc_snapshot_tables_host': (_int, [_p, _u64, _p, _p, _p, _p, _p, _p]),
+    'rc_snapshot_b64_device': (_int, [_p, _u64, _p, _p, _p, _p, _p]),
+    'rc_snapshot_timing_enable': (_int, [_p, _int]),
+    'rc_snapshot_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                       ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
 }
 
 

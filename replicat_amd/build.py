@@ -23,14 +23,16 @@ LIB = os.path.join(HERE, 'libreplicat_chunker.so')
 SOURCES = [os.path.join(CSRC, n) for n in ('kernels.hip', 'capi.cpp', 'blake2b.hip', 'capi_digest.cpp', 'gcm.hip',
                                              'capi_cipher.cpp', 'chacha.hip', 'capi_chacha.cpp', 'cipher_host.cpp',
                                              'sha2.hip', 'sha3.hip', 'restore.hip', 'capi_restore.cpp',
-                                             'index.hip', 'capi_index.cpp', 'gc.hip', 'capi_gc.cpp')]
+                                             'index.hip', 'capi_index.cpp', 'gc.hip', 'capi_gc.cpp', 'snapshot.hip',
+                                             'capi_snapshot.cpp')]
 HEADERS = [os.path.join(CSRC, n) for n in ('gclmul.h', 'digest_kernels.h', 'capi_internal.h', 'cipher_kernels.h',
                                              'knobs.h', 'diag.h', 'cipher_host.h', 'chacha_kernels.h',
                                              'poly1305_limbs.h', 'sha_kernels.h', 'sha_walk.h',
                                              'restore_kernels.h', 'index_kernels.h', 'index_lookup.h',
-                                             'blake2b_lane.h', 'gc_kernels.h')] + [
+                                             'blake2b_lane.h', 'gc_kernels.h', 'snapshot_kernels.h')] + [
     os.path.join(ROOT, 'include', n) for n in ('replicat_chunker.h', 'replicat_digest.h', 'replicat_cipher.h',
-                                               'replicat_restore.h', 'replicat_index.h', 'replicat_gc.h')]
+                                               'replicat_restore.h', 'replicat_index.h', 'replicat_gc.h',
+                                               'replicat_snapshot.h')]
 ARCH = 'gfx950'
 # -amdgpu-atomic-optimizer-strategy=None: the tile kernel's one-lane grab of its next work unit
 # must stay a plain global_atomic_add whose result is read a unit later; the optimizer rewrites a

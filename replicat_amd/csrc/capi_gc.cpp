@@ -196,6 +196,32 @@ int rc_gc_reference_host(rc_gc *g, uint64_t n, const uint8_t *digests) {
     return RC_OK;
 }
 
+int rc_gc_reference_device(rc_gc *g, uint64_t n, const uint8_t *d_digests) {
+    if (!g) return rc_fail(RC_ERR_ARGUMENT, "null gc");
+    if (n && !d_digests) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    if (reinterpret_cast<uintptr_t>(d_digests) & 7) return rc_fail(RC_ERR_ALIGN, "d_digests is not 8-byte aligned");
+    std::lock_guard<std::mutex> lock(g->mu);
+    rc::DeviceGuard guard(g->device);
+    std::vector<int64_t> owners;
+    for (uint64_t off = 0; off < n; off += RC_GC_BATCH) {
+        const uint64_t nb = std::min<uint64_t>(RC_GC_BATCH, n - off);
+        // unkeyed, the slots are the keys where they lie: the index reads name_bytes of a slot
+        const uint8_t *d_keys = d_digests + kIndexSlot * off;
+        if (g->d_mac) {
+            if (int rc = g->d_names.ensure(nb * kIndexSlot)) return rc;
+            const uint8_t *d_batch = d_keys;
+            if (int rc = rc::timed(g->t_names, nullptr, [&] {
+                    return rc_gc_launch_names(g->d_mac, nb, d_batch, g->digest_bytes, true, nullptr, 0,
+                                              static_cast<uint8_t *>(g->d_names.p), nullptr, nullptr);
+                }))
+                return rc;
+            d_keys = static_cast<const uint8_t *>(g->d_names.p);
+        }
+        if (int rc = resolve_batch(g, d_keys, nb, owners)) return rc;
+    }
+    return RC_OK;
+}
+
 int rc_gc_sweep_device(rc_gc *g, uint64_t n, const uint8_t *d_names, const uint8_t *d_tags,
                        uint64_t index_base, uint8_t *d_verdict, uint64_t *d_delete_idx,
                        uint64_t *d_n_delete, void *hip_stream) {

@@ -1,0 +1,355 @@
+// capi_snapshot.cpp -- host side of include/replicat_snapshot.h: the chunk tables of snapshot
+// bodies, decrypted and decoded on the device.
+//
+// A handle mirrors the `chunks` half of `_decrypt_snapshot_body` (replicat/repository.py:1001-1012)
+// for many snapshots per call.  Like rc_restore it owns no heavy kernel beyond its own stage: the
+// subkeys come from blake2b.hip's keyed update over the KDF state, the plaintexts and tag verdicts
+// from the borrowed cipher core, the wipe of what did not authenticate from restore.hip's verdict
+// kernel (given one buffer as both digests, it is exactly "zero where the tag failed").  Its own
+// are snapshot.hip's two decoders, the work lists they read and the event pairs around each stage.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "capi_internal.h"
+#include "cipher_host.h"
+#include "digest_kernels.h"
+#include "restore_kernels.h"
+#include "snapshot_kernels.h"
+
+static_assert(RC_TABLE_OK == RC_CHUNK_OK && RC_TABLE_BAD_TAG == RC_CHUNK_BAD_TAG,
+              "the verdict kernel writes the first two table statuses");
+
+struct rc_snapshot {
+    rc_cipher::CipherCore *cipher = nullptr;  // null: RC_CIPHER_NONE
+    int device = 0;
+    uint32_t digest_bytes = 0, stride = 0, overhead = 0;
+    std::mutex mu;
+    rc::DevBuf d_kdf;  // the rc_blake2b_state of the shared-subkey KDF
+    struct Staging {
+        rc::PinnedBuf h_stage;  // the work lists of one call, in the order the kernels read them
+        rc::DevBuf d_stage;     // their device copy
+        rc::DevBuf d_scratch;   // keys[64 n] | ok[n]
+    };
+    rc::SlotRing<Staging> ring;
+    // blocking host path
+    rc::DevBuf d_in, d_out, d_meta, d_slots;  // blobs | plaintexts | data digests[64 n] status[n] | digests
+    rc::PairTimer t_crypt, t_decode, t_b64;
+};
+
+namespace {
+
+using rc::up16;
+
+uint64_t table_count(uint32_t stride, uint64_t plain_len) {
+    if (plain_len == 2) return 0;
+    if (plain_len < 1 + uint64_t(stride) || (plain_len - 1) % stride) return kSnapReject;
+    return (plain_len - 1) / stride;
+}
+
+// blocks[]: one entry per workgroup, `per` units (records, characters) each, at least one per item
+template <class Units>
+void list_blocks(uint64_t n, uint64_t per, Units units, std::vector<SnapBlock> &blocks) {
+    blocks.clear();
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t u = units(i);
+        const uint64_t nb = u == kSnapReject || u == 0 ? 1 : (u + per - 1) / per;
+        for (uint64_t b = 0; b < nb; ++b) blocks.push_back(SnapBlock{uint32_t(i), uint32_t(b)});
+    }
+}
+
+// the caller holds s->mu and has the device current
+int tables_locked(rc_snapshot *s, uint64_t n, const uint8_t *const *d_blobs, const uint64_t *blob_lens,
+                  const uint8_t *d_data_digests, uint8_t *const *d_plain, uint64_t *counts,
+                  uint8_t *d_digests, uint8_t *d_status, hipStream_t st) {
+    const bool enc = s->cipher != nullptr;
+    std::vector<uint64_t> plain_lens(n);
+    std::vector<SnapTable> tables(n);
+    uint64_t first = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        plain_lens[i] = blob_lens[i] > s->overhead ? blob_lens[i] - s->overhead : 0;
+        const uint64_t c = table_count(s->stride, plain_lens[i]);
+        counts[i] = c == kSnapReject ? 0 : c;
+        tables[i] = SnapTable{reinterpret_cast<uint64_t>(enc ? d_plain[i] : d_blobs[i]), plain_lens[i], c, first};
+        first += counts[i];
+    }
+    std::vector<SnapBlock> blocks;
+    list_blocks(n, kSnapThreads, [&](uint64_t i) { return tables[i].count; }, blocks);
+    rc::SlotRing<rc_snapshot::Staging>::Slot *w = nullptr;
+    if (int rc = s->ring.acquire(w)) return rc;
+    // B2UItem[n] | RestorePlain[n] | SnapTable[n] | SnapBlock[]
+    const size_t plain_off = enc ? up16(n * sizeof(B2UItem)) : 0;
+    const size_t table_off = enc ? plain_off + up16(n * sizeof(RestorePlain)) : 0;
+    const size_t block_off = table_off + up16(n * sizeof(SnapTable));
+    const size_t stage = block_off + blocks.size() * sizeof(SnapBlock);
+    if (int rc = w->h_stage.ensure(stage)) return rc;
+    if (int rc = w->d_stage.ensure(stage)) return rc;
+    if (int rc = w->d_scratch.ensure(n * (kB2Slot + 1))) return rc;
+    uint8_t *h = static_cast<uint8_t *>(w->h_stage.p);
+    uint8_t *d = static_cast<uint8_t *>(w->d_stage.p);
+    uint8_t *d_keys = static_cast<uint8_t *>(w->d_scratch.p);
+    uint8_t *d_ok = d_keys + n * kB2Slot;
+    if (enc) {
+        B2UItem *it = reinterpret_cast<B2UItem *>(h);
+        RestorePlain *pl = reinterpret_cast<RestorePlain *>(h + plain_off);
+        const uint64_t state = reinterpret_cast<uint64_t>(s->d_kdf.p);
+        for (uint64_t i = 0; i < n; ++i) {
+            // derive_shared_subkey: hash_digest(body['data']) is the message, key slot i the output
+            it[i] = B2UItem{reinterpret_cast<uint64_t>(d_data_digests + kB2Slot * i), s->digest_bytes, i, state, 1u, 0u};
+            pl[i] = RestorePlain{reinterpret_cast<uint64_t>(d_plain[i]), plain_lens[i]};
+        }
+    }
+    std::memcpy(h + table_off, tables.data(), n * sizeof(SnapTable));
+    std::memcpy(h + block_off, blocks.data(), blocks.size() * sizeof(SnapBlock));
+    RC_HIP_TRY(hipMemcpyAsync(d, h, stage, hipMemcpyHostToDevice, st));
+    if (enc) {
+        RestoreVerdictArgs a{};
+        a.ok = d_ok;
+        a.computed = a.expected = d_keys;  // equal: the verdict is the tag's alone
+        a.plain = reinterpret_cast<const RestorePlain *>(d + plain_off);
+        a.status = d_status;
+        a.n = n;
+        a.digest_size = 1;
+        if (int rc = rc::timed(s->t_crypt, st, [&] {
+                if (int rc = rc_b2_launch_update(reinterpret_cast<const B2UItem *>(d), n, d_keys, st)) return rc;
+                std::vector<const uint8_t *> keys(n);
+                for (uint64_t i = 0; i < n; ++i) keys[i] = d_keys + kB2Slot * i;
+                if (int rc = rc_cipher::decrypt_device(s->cipher, n, d_blobs, blob_lens, keys.data(), d_plain, d_ok, st))
+                    return rc;
+                return rc_restore_launch_verdict(a, st);
+            }))
+            return rc;
+    } else {
+        RC_HIP_TRY(hipMemsetAsync(d_status, RC_TABLE_OK, n, st));
+    }
+    if (int rc = rc::timed(s->t_decode, st, [&] {
+            return rc_snap_launch_tables(reinterpret_cast<const SnapTable *>(d + table_off),
+                                         reinterpret_cast<const SnapBlock *>(d + block_off), blocks.size(),
+                                         s->digest_bytes, d_digests, d_status, st);
+        }))
+        return rc;
+    return s->ring.finish(*w, st);
+}
+
+int check_lists(const rc_snapshot *s, uint64_t n, const uint8_t *const *blobs, const uint64_t *lens,
+                const void *data_digests, uint8_t *const *plain, const void *counts, const void *digests,
+                const void *status) {
+    if (!blobs || !lens || !counts || !status || (s->cipher && (!plain || !data_digests)))
+        return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    if (n > 0xFFFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "more than 2^32 tables in one call");
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if ((lens[i] && !blobs[i]) || (s->cipher && lens[i] > s->overhead && !plain[i]))
+            return rc_fail(RC_ERR_ARGUMENT, "table %llu: null pointer", (unsigned long long)i);
+        if (s->cipher && lens[i] > s->overhead)
+            if (int rc = rc_cipher::check_len(s->cipher->desc, i, lens[i] - s->overhead)) return rc;
+        const uint64_t c = table_count(s->stride, lens[i] > s->overhead ? lens[i] - s->overhead : 0);
+        total += c == kSnapReject ? 0 : c;
+    }
+    if (total && !digests) return rc_fail(RC_ERR_ARGUMENT, "null digests");
+    if (reinterpret_cast<uintptr_t>(digests) & 15) return rc_fail(RC_ERR_ALIGN, "d_digests is not 16-byte aligned");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rc_snapshot_create(uint32_t digest_bytes, int cipher, void *cipher_handle,
+                       const rc_blake2b_state *kdf_state, int device, rc_snapshot **out) {
+    if (!out) return rc_fail(RC_ERR_ARGUMENT, "null output handle");
+    *out = nullptr;
+    if (digest_bytes < 1 || digest_bytes > RC_DIGEST_SLOT)
+        return rc_fail(RC_ERR_ARGUMENT, "digest_bytes must be 1..64, not %u", digest_bytes);
+    if (cipher != RC_CIPHER_NONE && cipher != RC_CIPHER_AES_GCM && cipher != RC_CIPHER_CHACHA20_POLY1305)
+        return rc_fail(RC_ERR_ARGUMENT, "unknown cipher code %d", cipher);
+    if (cipher == RC_CIPHER_NONE && (cipher_handle || kdf_state))
+        return rc_fail(RC_ERR_ARGUMENT, "a cipher handle or KDF state without a cipher");
+    if (cipher != RC_CIPHER_NONE && !cipher_handle) return rc_fail(RC_ERR_ARGUMENT, "null cipher handle");
+    if (cipher != RC_CIPHER_NONE && !kdf_state)
+        return rc_fail(RC_ERR_ARGUMENT, "a cipher needs the shared-subkey KDF state");
+    rc_cipher::CipherCore *core = nullptr;
+    if (cipher == RC_CIPHER_AES_GCM) core = rc_cipher::core_of(static_cast<rc_gcm *>(cipher_handle));
+    if (cipher == RC_CIPHER_CHACHA20_POLY1305) core = rc_cipher::core_of(static_cast<rc_chacha *>(cipher_handle));
+    if (core) {
+        if (core->device != device)
+            return rc_fail(RC_ERR_ARGUMENT, "loader on device %d, cipher on device %d", device, core->device);
+        if (kdf_state->digest_size != core->desc.key_bytes)
+            return rc_fail(RC_ERR_ARGUMENT, "KDF state derives %u bytes, the cipher's keys have %u",
+                           kdf_state->digest_size, core->desc.key_bytes);
+    } else if (int rc = rc::check_device(device)) {
+        return rc;
+    }
+    rc::DeviceGuard guard(device);
+    rc_snapshot *s = new rc_snapshot;
+    s->cipher = core;
+    s->device = device;
+    s->digest_bytes = digest_bytes;
+    s->stride = rc_snap_stride(digest_bytes);
+    s->overhead = core ? core->desc.nonce_bytes + 16 : 0;
+    auto setup = [s, kdf_state]() -> int {
+        if (int rc = s->ring.create()) return rc;
+        if (s->cipher) {
+            if (int rc = s->d_kdf.ensure(sizeof *kdf_state)) return rc;
+            RC_HIP_TRY(hipMemcpy(s->d_kdf.p, kdf_state, sizeof *kdf_state, hipMemcpyHostToDevice));
+        }
+        return 0;
+    };
+    if (int rc = setup()) {
+        rc_snapshot_destroy(s);
+        return rc;
+    }
+    rc_track(s, [](void *p) { rc_snapshot_destroy(static_cast<rc_snapshot *>(p)); });
+    *out = s;
+    return RC_OK;
+}
+
+void rc_snapshot_destroy(rc_snapshot *s) {
+    if (!s) return;
+    rc::teardown(s, [s] {
+        s->ring.release([](rc_snapshot::Staging &w) {
+            w.h_stage.release();
+            w.d_stage.release();
+            w.d_scratch.release();
+        });
+        for (rc::DevBuf *b : {&s->d_kdf, &s->d_in, &s->d_out, &s->d_meta, &s->d_slots}) b->release();
+        for (rc::PairTimer *t : {&s->t_crypt, &s->t_decode, &s->t_b64}) t->release();
+    });
+    delete s;
+}
+
+uint32_t rc_snapshot_stride(const rc_snapshot *s) { return s ? s->stride : 0; }
+uint32_t rc_snapshot_overhead(const rc_snapshot *s) { return s ? s->overhead : 0; }
+
+uint64_t rc_snapshot_table_count(const rc_snapshot *s, uint64_t plain_len) {
+    return s ? table_count(s->stride, plain_len) : kSnapReject;
+}
+
+uint64_t rc_snapshot_table_count_for(uint32_t digest_bytes, uint64_t plain_len) {
+    if (digest_bytes < 1 || digest_bytes > RC_DIGEST_SLOT) return kSnapReject;
+    return table_count(rc_snap_stride(digest_bytes), plain_len);
+}
+
+int rc_snapshot_tables_device(rc_snapshot *s, uint64_t n, const uint8_t *const *d_blobs,
+                              const uint64_t *blob_lens, const uint8_t *d_data_digests,
+                              uint8_t *const *d_plain, uint64_t *counts, uint8_t *d_digests,
+                              uint8_t *d_status, void *hip_stream) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    if (n == 0) return RC_OK;
+    if (int rc = check_lists(s, n, d_blobs, blob_lens, d_data_digests, d_plain, counts, d_digests, d_status))
+        return rc;
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    return tables_locked(s, n, d_blobs, blob_lens, d_data_digests, d_plain, counts, d_digests, d_status,
+                         static_cast<hipStream_t>(hip_stream));
+}
+
+int rc_snapshot_tables_host(rc_snapshot *s, uint64_t n, const uint8_t *const *blobs, const uint64_t *lens,
+                            const uint8_t *data_digests, uint64_t *counts, uint8_t *digests, uint8_t *status) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    if (n == 0) return RC_OK;
+    const bool enc = s->cipher != nullptr;
+    if (!blobs || !lens || !counts || !status || (enc && !data_digests)) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    if (n > 0xFFFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "more than 2^32 tables in one call");
+    uint64_t slots = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (lens[i] && !blobs[i]) return rc_fail(RC_ERR_ARGUMENT, "table %llu: null pointer", (unsigned long long)i);
+        if (enc && lens[i] > s->overhead)
+            if (int rc = rc_cipher::check_len(s->cipher->desc, i, lens[i] - s->overhead)) return rc;
+        const uint64_t c = table_count(s->stride, lens[i] > s->overhead ? lens[i] - s->overhead : 0);
+        slots += c == kSnapReject ? 0 : c;
+    }
+    if (slots && !digests) return rc_fail(RC_ERR_ARGUMENT, "null digests");
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    // blob i and its plaintext share an offset (16-aligned: AES-GCM's vector path)
+    std::vector<uint64_t> off;
+    const uint64_t total = rc::offsets16(n, lens, off);
+    if (int rc = s->d_in.ensure(total + 16)) return rc;
+    if (enc)
+        if (int rc = s->d_out.ensure(total + 16)) return rc;
+    if (int rc = s->d_meta.ensure(n * (kB2Slot + 1))) return rc;
+    if (int rc = s->d_slots.ensure(slots * RC_DIGEST_SLOT)) return rc;
+    const hipStream_t st = nullptr;
+    uint8_t *in = static_cast<uint8_t *>(s->d_in.p), *outp = static_cast<uint8_t *>(s->d_out.p);
+    uint8_t *d_dd = static_cast<uint8_t *>(s->d_meta.p), *d_status = d_dd + n * kB2Slot;
+    std::vector<const uint8_t *> dp(n);
+    std::vector<uint8_t *> dq(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        dp[i] = in + off[i];
+        dq[i] = enc ? outp + off[i] : nullptr;
+        if (lens[i]) RC_HIP_TRY(hipMemcpyAsync(in + off[i], blobs[i], lens[i], hipMemcpyHostToDevice, st));
+    }
+    if (enc) RC_HIP_TRY(hipMemcpyAsync(d_dd, data_digests, n * kB2Slot, hipMemcpyHostToDevice, st));
+    if (int rc = tables_locked(s, n, dp.data(), lens, d_dd, enc ? dq.data() : nullptr, counts,
+                               static_cast<uint8_t *>(s->d_slots.p), d_status, st))
+        return rc;
+    std::vector<uint8_t> image(slots * RC_DIGEST_SLOT);
+    if (slots) RC_HIP_TRY(hipMemcpyAsync(image.data(), s->d_slots.p, image.size(), hipMemcpyDeviceToHost, st));
+    RC_HIP_TRY(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, st));
+    RC_HIP_TRY(hipStreamSynchronize(st));
+    for (uint64_t k = 0; k < slots; ++k)
+        std::memcpy(digests + k * s->digest_bytes, image.data() + k * RC_DIGEST_SLOT, s->digest_bytes);
+    for (uint64_t i = 0; i < n; ++i)
+        if (status[i] == RC_TABLE_BAD_TAG) return rc_fail(RC_ERR_TAG, "tag mismatch (InvalidTag)");
+    return RC_OK;
+}
+
+int rc_snapshot_b64_device(rc_snapshot *s, uint64_t n, const uint8_t *const *d_texts, const uint64_t *text_lens,
+                           uint8_t *const *d_out, uint8_t *d_ok, void *hip_stream) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    if (n == 0) return RC_OK;
+    if (!d_texts || !text_lens || !d_out || !d_ok) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    if (n > 0xFFFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "more than 2^32 texts in one call");
+    std::vector<SnapText> texts(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        if (text_lens[i] && (!d_texts[i] || (text_lens[i] >= 4 && !d_out[i])))
+            return rc_fail(RC_ERR_ARGUMENT, "text %llu: null pointer", (unsigned long long)i);
+        if (text_lens[i] > (uint64_t(1) << 43))
+            return rc_fail(RC_ERR_ARGUMENT, "text %llu: longer than 2^43 characters", (unsigned long long)i);
+        texts[i] = SnapText{reinterpret_cast<uint64_t>(d_texts[i]), text_lens[i] % 4 ? kSnapReject : text_lens[i],
+                            reinterpret_cast<uint64_t>(d_out[i])};
+    }
+    std::vector<SnapBlock> blocks;
+    list_blocks(n, uint64_t(kSnapThreads) * kSnapLaneChars, [&](uint64_t i) { return texts[i].len; }, blocks);
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    rc::SlotRing<rc_snapshot::Staging>::Slot *w = nullptr;
+    if (int rc = s->ring.acquire(w)) return rc;
+    const size_t block_off = up16(n * sizeof(SnapText));
+    const size_t stage = block_off + blocks.size() * sizeof(SnapBlock);
+    if (int rc = w->h_stage.ensure(stage)) return rc;
+    if (int rc = w->d_stage.ensure(stage)) return rc;
+    uint8_t *h = static_cast<uint8_t *>(w->h_stage.p);
+    uint8_t *d = static_cast<uint8_t *>(w->d_stage.p);
+    std::memcpy(h, texts.data(), n * sizeof(SnapText));
+    std::memcpy(h + block_off, blocks.data(), blocks.size() * sizeof(SnapBlock));
+    RC_HIP_TRY(hipMemcpyAsync(d, h, stage, hipMemcpyHostToDevice, st));
+    RC_HIP_TRY(hipMemsetAsync(d_ok, 1, n, st));
+    if (int rc = rc::timed(s->t_b64, st, [&] {
+            return rc_snap_launch_b64(reinterpret_cast<const SnapText *>(d),
+                                      reinterpret_cast<const SnapBlock *>(d + block_off), blocks.size(), d_ok, st);
+        }))
+        return rc;
+    return s->ring.finish(*w, st);
+}
+
+int rc_snapshot_timing_enable(rc_snapshot *s, int enable) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    return rc::timing_enable(s, {&s->t_crypt, &s->t_decode, &s->t_b64}, enable);
+}
+
+int rc_snapshot_timing_read(rc_snapshot *s, double *crypt_ms, double *decode_ms, double *b64_ms,
+                            uint64_t *decode_calls) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    if (int rc = s->t_crypt.read(crypt_ms, nullptr)) return rc;
+    if (int rc = s->t_b64.read(b64_ms, nullptr)) return rc;
+    return s->t_decode.read(decode_ms, decode_calls);
+}
+
+}  // extern "C"

@@ -202,6 +202,12 @@ class GpuChunkGC:
         arr = _rows(digests, self.digest_size, 'digest')
         check(lib().rc_gc_reference_host(self._handle(), len(arr), _ptr(arr)))
 
+    def reference_device(self, slots_ptr: int, n: int):
+        """``reference`` for n digests already on the device, in 64-byte slots from the raw
+        pointer ``slots_ptr`` (bytes past digest_size in a slot are ignored).  The work that wrote
+        them must have completed."""
+        check(lib().rc_gc_reference_device(self._handle(), int(n), int(slots_ptr) if n else None))
+
     def sweep(self, names, tags) -> Tuple[np.ndarray, np.ndarray]:
         """clean's verdict for listed (name, tag) pairs: (verdict, delete_idx), the uint8 verdict
         of every pair (REFERENCED, DELETE, TAG_MISMATCH) and the ascending uint64 indices of the

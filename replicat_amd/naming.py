@@ -17,6 +17,7 @@ import posixpath
 from typing import Iterable, Iterator, NamedTuple, Optional, Tuple
 
 CHUNK_PREFIX = 'data/'
+SNAPSHOT_PREFIX = 'snapshots/'
 
 
 class LocationParts(NamedTuple):
@@ -36,6 +37,20 @@ def parse_chunk_location(location: str) -> LocationParts:
     head, _, name = location.rpartition('-')
     parts = head.rsplit('/', 3)
     return LocationParts(name=name, tag=parts[1] + parts[2] + parts[3])
+
+
+def snapshot_location(name: str, tag: str) -> str:
+    """get_snapshot_location (repository.py:483-491): name and tag are hex strings."""
+    return posixpath.join(SNAPSHOT_PREFIX, tag[:2], f'{tag[2:]}-{name}')
+
+
+def parse_snapshot_location(location: str) -> LocationParts:
+    """parse_snapshot_location (repository.py:493-499)."""
+    if not location.startswith(SNAPSHOT_PREFIX):
+        raise ValueError('Not a snapshot location')
+    head, _, name = location.rpartition('-')
+    parts = head.rsplit('/', 2)
+    return LocationParts(name=name, tag=parts[1] + parts[2])
 
 
 def names_from_locations(locations: Iterable[str], name_bytes: Optional[int] = None) -> Iterator[bytes]:
@@ -92,4 +107,4 @@ class ChunkNaming:
 
 
 __all__ = ['ChunkNaming', 'LocationParts', 'CHUNK_PREFIX', 'chunk_location', 'parse_chunk_location',
-           'names_from_locations']
+           'names_from_locations', 'SNAPSHOT_PREFIX', 'snapshot_location', 'parse_snapshot_location']
