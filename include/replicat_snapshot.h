@@ -116,6 +116,66 @@ int rc_snapshot_timing_enable(rc_snapshot *s, int enable);
 int rc_snapshot_timing_read(rc_snapshot *s, double *crypt_ms, double *decode_ms, double *b64_ms,
                             uint64_t *decode_calls);
 
+/* ---------------------------------------------------------------------------------------------
+ * Writing: the `chunks` half of `_encrypt_snapshot_body` (replicat/repository.py:982-999) on the
+ * same handle -- digests in device slots to the table text serialize writes, sealed under the
+ * subkey derived from hash_digest(encrypted data) -- and the bulk base64 ENCODE of the two fields
+ * of an encrypted snapshot file.  Kernels: replicat_amd/csrc/snapshot_write.hip.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Host only: the bytes of the table of `count` digests -- 2 for count 0, else 1 + count * stride;
+ * the exact inverse of rc_snapshot_table_count.  UINT64_MAX for a NULL handle or when the length
+ * does not fit 64 bits. */
+uint64_t rc_snapshot_table_len(const rc_snapshot *s, uint64_t count);
+/* The same without a handle, for digests of digest_bytes bytes (UINT64_MAX outside 1..64). */
+uint64_t rc_snapshot_table_len_for(uint32_t digest_bytes, uint64_t count);
+
+/* Host only: the characters of the base64 of nbytes bytes, 4 ceil(nbytes / 3), or UINT64_MAX
+ * when that does not fit 64 bits. */
+uint64_t rc_snapshot_b64_len(uint64_t nbytes);
+
+/* Bulk base64: encode n DEVICE buffers d_in[i] of lens[i] bytes (HOST arrays of pointers and
+ * lengths) into d_out[i] (DEVICE): exactly rc_snapshot_b64_len(lens[i]) characters of the
+ * standard alphabet are written there, '=' only as the last one or two, and nothing else.
+ * Source and destination may have any alignment: the kernel reads whole aligned 16-byte granules
+ * that hold at least one byte of a source.  Enqueued on hip_stream, no synchronisation. */
+int rc_snapshot_b64_encode_device(rc_snapshot *s, uint64_t n, const uint8_t *const *d_in,
+                                  const uint64_t *lens, uint8_t *const *d_out, void *hip_stream);
+
+/* Seal n tables.  Table i is the counts[i] 64-byte slots from slot firsts[i] of d_digests
+ * (DEVICE, 16-byte aligned; only the first digest_bytes bytes of a slot take part; firsts and
+ * counts are HOST arrays).  On hip_stream, with no host synchronisation in between, this enqueues
+ *   1. the text of every table into d_text[i] (DEVICE; exactly rc_snapshot_table_len(counts[i])
+ *      bytes are written, at any alignment);
+ *   2. the subkey of every table from the 64-byte slot d_data_digests + 64 i (DEVICE; its first
+ *      digest_bytes bytes are hash_digest(encrypted data)): the derivation and the key slots of
+ *      rc_snapshot_tables_device step 1;
+ *   3. the encryption of text i under that subkey and the nonce at d_nonces + nonce_bytes i
+ *      (DEVICE) into d_blobs[i] (DEVICE): nonce || C || T, table_len + overhead bytes.
+ * With RC_CIPHER_NONE steps 2 and 3 fall away and d_data_digests, d_nonces and d_blobs are
+ * ignored (may be NULL).  Scratch memory alternates between two workspaces, as in
+ * rc_snapshot_tables_device.  RC_ERR_ARGUMENT, before any device is touched: a NULL handle; NULL
+ * arrays with n > 0; a NULL d_nonces, d_data_digests or d_blobs with a cipher; a table longer
+ * than the cipher's longest message. */
+int rc_snapshot_seal_tables_device(rc_snapshot *s, uint64_t n, const uint8_t *d_digests,
+                                   const uint64_t *firsts, const uint64_t *counts,
+                                   const uint8_t *d_data_digests, const uint8_t *d_nonces,
+                                   uint8_t *const *d_text, uint8_t *const *d_blobs, void *hip_stream);
+
+/* The same over HOST buffers, blocking: digests (sum(counts) digests of digest_bytes bytes back to
+ * back, table after table), counts[n], data_digests (n 64-byte slots) and nonces (n nonces of
+ * nonce_bytes back to back), both ignored with RC_CIPHER_NONE; out[i] receives blob i
+ * (table_len + overhead bytes), or without a cipher the text of table i. */
+int rc_snapshot_seal_tables_host(rc_snapshot *s, uint64_t n, const uint8_t *digests,
+                                 const uint64_t *counts, const uint8_t *data_digests,
+                                 const uint8_t *nonces, uint8_t *const *out);
+
+/* The writing side of the kernel timing rc_snapshot_timing_enable switches on: the summed
+ * milliseconds of the table encodes (encode_ms, and their number in encode_calls), of the bulk
+ * base64 encodes (b64_ms) and of the subkey and encrypt work (crypt_ms); clears them. */
+int rc_snapshot_write_timing_read(rc_snapshot *s, double *encode_ms, double *b64_ms, double *crypt_ms,
+                                  uint64_t *encode_calls);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,8 @@ __version__ = '0.3.0'
 
 _GC_EXPORTS = ('GpuChunkGC', 'CleanPlan')
 _SNAPSHOTS_EXPORTS = ('GpuSnapshotLoader', 'LoadedSnapshot')
-__all__ = list(_GC_EXPORTS + _SNAPSHOTS_EXPORTS)
+_SNAPSHOT_WRITE_EXPORTS = ('GpuSnapshotWriter', 'WrittenSnapshot', 'DeviceDigests')
+__all__ = list(_GC_EXPORTS + _SNAPSHOTS_EXPORTS + _SNAPSHOT_WRITE_EXPORTS)
 
 
 def __getattr__(name):
@@ -23,4 +24,7 @@ def __getattr__(name):
     if name in _SNAPSHOTS_EXPORTS:  # snapshot loading (replicat_amd/snapshots.py), likewise
         from . import snapshots
         return getattr(snapshots, name)
+    if name in _SNAPSHOT_WRITE_EXPORTS:  # snapshot writing (replicat_amd/snapshot_write.py)
+        from . import snapshot_write
+        return getattr(snapshot_write, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

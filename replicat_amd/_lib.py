@@ -184,6 +184,14 @@ SIGNATURES = {
     'rc_snapshot_timing_enable': (_int, [_p, _int]),
     'rc_snapshot_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
+    'rc_snapshot_table_len': (_u64, [_p, _u64]),
+    'rc_snapshot_table_len_for': (_u64, [_u32, _u64]),
+    'rc_snapshot_b64_len': (_u64, [_u64]),
+    'rc_snapshot_b64_encode_device': (_int, [_p, _u64, _p, _p, _p, _p]),
+    'rc_snapshot_seal_tables_device': (_int, [_p, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'rc_snapshot_seal_tables_host': (_int, [_p, _u64, _p, _p, _p, _p, _p]),
+    'rc_snapshot_write_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
 }
 
 

@@ -37,6 +37,9 @@ struct rc_snapshot {
     // blocking host path
     rc::DevBuf d_in, d_out, d_meta, d_slots;  // blobs | plaintexts | data digests[64 n] status[n] | digests
     rc::PairTimer t_crypt, t_decode, t_b64;
+    // writing (snapshot_write.hip)
+    rc::DevBuf d_nonces;  // blocking host path: the nonces of one call
+    rc::PairTimer t_encode, t_b64_encode, t_seal;
 };
 
 namespace {
@@ -153,6 +156,87 @@ int check_lists(const rc_snapshot *s, uint64_t n, const uint8_t *const *blobs, c
     return 0;
 }
 
+// ------------------------------------------------------------------------------------ writing
+
+// the inverse of table_count
+uint64_t table_len(uint32_t stride, uint64_t count) {
+    if (count == 0) return 2;
+    if (count > (kSnapReject - 1) / stride) return kSnapReject;
+    return 1 + count * stride;
+}
+
+uint64_t b64_len(uint64_t nbytes) {
+    const uint64_t groups = nbytes / 3 + (nbytes % 3 ? 1 : 0);
+    return groups > kSnapReject / 4 ? kSnapReject : 4 * groups;
+}
+
+// What both seal calls check before a device is touched; lens[i] = the length of text i.
+int check_seal(const rc_snapshot *s, uint64_t n, const uint64_t *counts, std::vector<uint64_t> &lens) {
+    if (n > 0xFFFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "more than 2^32 tables in one call");
+    lens.resize(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        lens[i] = table_len(s->stride, counts[i]);
+        if (lens[i] == kSnapReject)
+            return rc_fail(RC_ERR_ARGUMENT, "table %llu: %llu digests do not fit a text", (unsigned long long)i,
+                           (unsigned long long)counts[i]);
+        if (s->cipher)
+            if (int rc = rc_cipher::check_len(s->cipher->desc, i, lens[i])) return rc;
+    }
+    return 0;
+}
+
+// the caller holds s->mu, has the device current and has run check_seal
+int seal_locked(rc_snapshot *s, uint64_t n, const uint8_t *d_digests, const uint64_t *firsts,
+                const uint64_t *counts, const uint64_t *lens, const uint8_t *d_data_digests,
+                const uint8_t *d_nonces, uint8_t *const *d_text, uint8_t *const *d_blobs, hipStream_t st) {
+    const bool enc = s->cipher != nullptr;
+    std::vector<SnapBlock> blocks;
+    list_blocks(n, kSnapThreads, [&](uint64_t i) { return counts[i]; }, blocks);
+    rc::SlotRing<rc_snapshot::Staging>::Slot *w = nullptr;
+    if (int rc = s->ring.acquire(w)) return rc;
+    // B2UItem[n] | SnapTable[n] | SnapBlock[]
+    const size_t table_off = enc ? up16(n * sizeof(B2UItem)) : 0;
+    const size_t block_off = table_off + up16(n * sizeof(SnapTable));
+    const size_t stage = block_off + blocks.size() * sizeof(SnapBlock);
+    if (int rc = w->h_stage.ensure(stage)) return rc;
+    if (int rc = w->d_stage.ensure(stage)) return rc;
+    if (enc)
+        if (int rc = w->d_scratch.ensure(n * kB2Slot)) return rc;
+    uint8_t *h = static_cast<uint8_t *>(w->h_stage.p);
+    uint8_t *d = static_cast<uint8_t *>(w->d_stage.p);
+    uint8_t *d_keys = static_cast<uint8_t *>(w->d_scratch.p);
+    SnapTable *tables = reinterpret_cast<SnapTable *>(h + table_off);
+    for (uint64_t i = 0; i < n; ++i) {
+        tables[i] = SnapTable{reinterpret_cast<uint64_t>(d_text[i]), lens[i], counts[i], firsts[i]};
+        if (enc) {
+            const uint64_t state = reinterpret_cast<uint64_t>(s->d_kdf.p);
+            reinterpret_cast<B2UItem *>(h)[i] =
+                B2UItem{reinterpret_cast<uint64_t>(d_data_digests + kB2Slot * i), s->digest_bytes, i, state, 1u, 0u};
+        }
+    }
+    std::memcpy(h + block_off, blocks.data(), blocks.size() * sizeof(SnapBlock));
+    RC_HIP_TRY(hipMemcpyAsync(d, h, stage, hipMemcpyHostToDevice, st));
+    if (int rc = rc::timed(s->t_encode, st, [&] {
+            return rc_snap_launch_encode_tables(reinterpret_cast<const SnapTable *>(d + table_off),
+                                                reinterpret_cast<const SnapBlock *>(d + block_off), blocks.size(),
+                                                s->digest_bytes, d_digests, st);
+        }))
+        return rc;
+    if (enc) {
+        if (int rc = rc::timed(s->t_seal, st, [&] {
+                if (int rc = rc_b2_launch_update(reinterpret_cast<const B2UItem *>(d), n, d_keys, st)) return rc;
+                std::vector<const uint8_t *> keys(n), nonces(n);
+                for (uint64_t i = 0; i < n; ++i) {
+                    keys[i] = d_keys + kB2Slot * i;
+                    nonces[i] = d_nonces + uint64_t(s->cipher->desc.nonce_bytes) * i;
+                }
+                return rc_cipher::encrypt_device(s->cipher, n, d_text, lens, keys.data(), nonces.data(), d_blobs, st);
+            }))
+            return rc;
+    }
+    return s->ring.finish(*w, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -214,8 +298,9 @@ void rc_snapshot_destroy(rc_snapshot *s) {
             w.d_stage.release();
             w.d_scratch.release();
         });
-        for (rc::DevBuf *b : {&s->d_kdf, &s->d_in, &s->d_out, &s->d_meta, &s->d_slots}) b->release();
-        for (rc::PairTimer *t : {&s->t_crypt, &s->t_decode, &s->t_b64}) t->release();
+        for (rc::DevBuf *b : {&s->d_kdf, &s->d_in, &s->d_out, &s->d_meta, &s->d_slots, &s->d_nonces}) b->release();
+        for (rc::PairTimer *t : {&s->t_crypt, &s->t_decode, &s->t_b64, &s->t_encode, &s->t_b64_encode, &s->t_seal})
+            t->release();
     });
     delete s;
 }
@@ -339,7 +424,8 @@ int rc_snapshot_b64_device(rc_snapshot *s, uint64_t n, const uint8_t *const *d_t
 
 int rc_snapshot_timing_enable(rc_snapshot *s, int enable) {
     if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
-    return rc::timing_enable(s, {&s->t_crypt, &s->t_decode, &s->t_b64}, enable);
+    return rc::timing_enable(s, {&s->t_crypt, &s->t_decode, &s->t_b64, &s->t_encode, &s->t_b64_encode, &s->t_seal},
+                             enable);
 }
 
 int rc_snapshot_timing_read(rc_snapshot *s, double *crypt_ms, double *decode_ms, double *b64_ms,
@@ -350,6 +436,147 @@ int rc_snapshot_timing_read(rc_snapshot *s, double *crypt_ms, double *decode_ms,
     if (int rc = s->t_crypt.read(crypt_ms, nullptr)) return rc;
     if (int rc = s->t_b64.read(b64_ms, nullptr)) return rc;
     return s->t_decode.read(decode_ms, decode_calls);
+}
+
+// ------------------------------------------------------------------------------------ writing
+
+uint64_t rc_snapshot_table_len(const rc_snapshot *s, uint64_t count) {
+    return s ? table_len(s->stride, count) : kSnapReject;
+}
+
+uint64_t rc_snapshot_table_len_for(uint32_t digest_bytes, uint64_t count) {
+    if (digest_bytes < 1 || digest_bytes > RC_DIGEST_SLOT) return kSnapReject;
+    return table_len(rc_snap_stride(digest_bytes), count);
+}
+
+uint64_t rc_snapshot_b64_len(uint64_t nbytes) { return b64_len(nbytes); }
+
+int rc_snapshot_b64_encode_device(rc_snapshot *s, uint64_t n, const uint8_t *const *d_in, const uint64_t *lens,
+                                  uint8_t *const *d_out, void *hip_stream) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    if (n == 0) return RC_OK;
+    if (!d_in || !lens || !d_out) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    if (n > 0xFFFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "more than 2^32 buffers in one call");
+    std::vector<SnapText> texts(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        if (lens[i] && (!d_in[i] || !d_out[i]))
+            return rc_fail(RC_ERR_ARGUMENT, "buffer %llu: null pointer", (unsigned long long)i);
+        if (lens[i] > (uint64_t(1) << 42))
+            return rc_fail(RC_ERR_ARGUMENT, "buffer %llu: longer than 2^42 bytes", (unsigned long long)i);
+        texts[i] = SnapText{reinterpret_cast<uint64_t>(d_in[i]), lens[i], reinterpret_cast<uint64_t>(d_out[i])};
+    }
+    std::vector<SnapBlock> blocks;
+    list_blocks(n, uint64_t(kSnapThreads) * kSnapLaneBytes, [&](uint64_t i) { return texts[i].len; }, blocks);
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    rc::SlotRing<rc_snapshot::Staging>::Slot *w = nullptr;
+    if (int rc = s->ring.acquire(w)) return rc;
+    const size_t block_off = up16(n * sizeof(SnapText));
+    const size_t stage = block_off + blocks.size() * sizeof(SnapBlock);
+    if (int rc = w->h_stage.ensure(stage)) return rc;
+    if (int rc = w->d_stage.ensure(stage)) return rc;
+    uint8_t *h = static_cast<uint8_t *>(w->h_stage.p);
+    uint8_t *d = static_cast<uint8_t *>(w->d_stage.p);
+    std::memcpy(h, texts.data(), n * sizeof(SnapText));
+    std::memcpy(h + block_off, blocks.data(), blocks.size() * sizeof(SnapBlock));
+    RC_HIP_TRY(hipMemcpyAsync(d, h, stage, hipMemcpyHostToDevice, st));
+    if (int rc = rc::timed(s->t_b64_encode, st, [&] {
+            return rc_snap_launch_b64_encode(reinterpret_cast<const SnapText *>(d),
+                                             reinterpret_cast<const SnapBlock *>(d + block_off), blocks.size(), st);
+        }))
+        return rc;
+    return s->ring.finish(*w, st);
+}
+
+int rc_snapshot_seal_tables_device(rc_snapshot *s, uint64_t n, const uint8_t *d_digests, const uint64_t *firsts,
+                                   const uint64_t *counts, const uint8_t *d_data_digests, const uint8_t *d_nonces,
+                                   uint8_t *const *d_text, uint8_t *const *d_blobs, void *hip_stream) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    if (n == 0) return RC_OK;
+    if (!firsts || !counts || !d_text) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    if (s->cipher && (!d_data_digests || !d_nonces || !d_blobs))
+        return rc_fail(RC_ERR_ARGUMENT, "a cipher needs data digests, nonces and blobs");
+    std::vector<uint64_t> lens;
+    if (int rc = check_seal(s, n, counts, lens)) return rc;
+    uint64_t slots = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (!d_text[i] || (s->cipher && !d_blobs[i]))
+            return rc_fail(RC_ERR_ARGUMENT, "table %llu: null pointer", (unsigned long long)i);
+        slots += counts[i];
+    }
+    if (slots && !d_digests) return rc_fail(RC_ERR_ARGUMENT, "null digests");
+    if (reinterpret_cast<uintptr_t>(d_digests) & 15) return rc_fail(RC_ERR_ALIGN, "d_digests is not 16-byte aligned");
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    return seal_locked(s, n, d_digests, firsts, counts, lens.data(), d_data_digests, d_nonces, d_text, d_blobs,
+                       static_cast<hipStream_t>(hip_stream));
+}
+
+int rc_snapshot_seal_tables_host(rc_snapshot *s, uint64_t n, const uint8_t *digests, const uint64_t *counts,
+                                 const uint8_t *data_digests, const uint8_t *nonces, uint8_t *const *out) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    if (n == 0) return RC_OK;
+    const bool enc = s->cipher != nullptr;
+    if (!counts || !out) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    if (enc && (!data_digests || !nonces)) return rc_fail(RC_ERR_ARGUMENT, "a cipher needs data digests and nonces");
+    std::vector<uint64_t> lens;
+    if (int rc = check_seal(s, n, counts, lens)) return rc;
+    std::vector<uint64_t> firsts(n), out_lens(n);
+    uint64_t slots = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (!out[i]) return rc_fail(RC_ERR_ARGUMENT, "table %llu: null pointer", (unsigned long long)i);
+        firsts[i] = slots;
+        slots += counts[i];
+        out_lens[i] = lens[i] + s->overhead;
+    }
+    if (slots && !digests) return rc_fail(RC_ERR_ARGUMENT, "null digests");
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    // text i and blob i share an offset in two images
+    std::vector<uint64_t> off;
+    const uint64_t total = rc::offsets16(n, out_lens.data(), off);
+    const uint32_t nonce_bytes = enc ? s->cipher->desc.nonce_bytes : 0;
+    if (int rc = s->d_in.ensure(total + 16)) return rc;
+    if (enc) {
+        if (int rc = s->d_out.ensure(total + 16)) return rc;
+        if (int rc = s->d_meta.ensure(n * kB2Slot)) return rc;
+        if (int rc = s->d_nonces.ensure(n * uint64_t(nonce_bytes))) return rc;
+    }
+    if (int rc = s->d_slots.ensure(slots * RC_DIGEST_SLOT)) return rc;
+    const hipStream_t st = nullptr;
+    std::vector<uint8_t> image(slots * RC_DIGEST_SLOT, 0);
+    for (uint64_t k = 0; k < slots; ++k)
+        std::memcpy(image.data() + k * RC_DIGEST_SLOT, digests + k * s->digest_bytes, s->digest_bytes);
+    if (slots) RC_HIP_TRY(hipMemcpyAsync(s->d_slots.p, image.data(), image.size(), hipMemcpyHostToDevice, st));
+    if (enc) {
+        RC_HIP_TRY(hipMemcpyAsync(s->d_meta.p, data_digests, n * kB2Slot, hipMemcpyHostToDevice, st));
+        RC_HIP_TRY(hipMemcpyAsync(s->d_nonces.p, nonces, n * uint64_t(nonce_bytes), hipMemcpyHostToDevice, st));
+    }
+    uint8_t *text = static_cast<uint8_t *>(s->d_in.p), *blob = static_cast<uint8_t *>(s->d_out.p);
+    std::vector<uint8_t *> dt(n), db(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        dt[i] = text + off[i];
+        db[i] = enc ? blob + off[i] : nullptr;
+    }
+    if (int rc = seal_locked(s, n, static_cast<const uint8_t *>(s->d_slots.p), firsts.data(), counts, lens.data(),
+                             static_cast<const uint8_t *>(s->d_meta.p), static_cast<const uint8_t *>(s->d_nonces.p),
+                             dt.data(), enc ? db.data() : nullptr, st))
+        return rc;
+    for (uint64_t i = 0; i < n; ++i)
+        RC_HIP_TRY(hipMemcpyAsync(out[i], (enc ? blob : text) + off[i], out_lens[i], hipMemcpyDeviceToHost, st));
+    RC_HIP_TRY(hipStreamSynchronize(st));
+    return RC_OK;
+}
+
+int rc_snapshot_write_timing_read(rc_snapshot *s, double *encode_ms, double *b64_ms, double *crypt_ms,
+                                  uint64_t *encode_calls) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    if (int rc = s->t_seal.read(crypt_ms, nullptr)) return rc;
+    if (int rc = s->t_b64_encode.read(b64_ms, nullptr)) return rc;
+    return s->t_encode.read(encode_ms, encode_calls);
 }
 
 }  // extern "C"

@@ -42,3 +42,19 @@ int rc_snap_launch_tables(const SnapTable *d_tables, const SnapBlock *d_blocks, 
 // others at their `out`.
 int rc_snap_launch_b64(const SnapText *d_texts, const SnapBlock *d_blocks, uint64_t n_blocks, uint8_t *d_ok,
                        hipStream_t stream);
+
+// snapshot_write.hip: the inverses.  A SnapTable is then a text to write (ptr, len = 1 + count *
+// stride, or 2) from the `count` slots first, first + 1, ... of d_slots; a SnapText `len` bytes at
+// ptr whose 4 ceil(len / 3) characters go to `out`; a block of the bulk encoder is kSnapThreads *
+// kSnapLaneBytes bytes.
+__global__ void rc_snap_encode_tables_kernel(const SnapTable *tables, const SnapBlock *blocks,
+                                             uint32_t digest_bytes, const uint8_t *slots);
+__global__ void rc_snap_b64_encode_kernel(const SnapText *texts, const SnapBlock *blocks);
+
+// Exactly tables[t].len bytes at each table's ptr; reads 64 bytes per digest.
+int rc_snap_launch_encode_tables(const SnapTable *d_tables, const SnapBlock *d_blocks, uint64_t n_blocks,
+                                 uint32_t digest_bytes, const uint8_t *d_slots, hipStream_t stream);
+
+// Exactly 4 ceil(len / 3) characters at each text's out.
+int rc_snap_launch_b64_encode(const SnapText *d_texts, const SnapBlock *d_blocks, uint64_t n_blocks,
+                              hipStream_t stream);

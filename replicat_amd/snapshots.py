@@ -31,7 +31,8 @@ reference yields, the type of the exception it raises included.  The pattern is 
 locations that are not canonical.
 
 Out of scope: the digest check of a freshly downloaded file (repository.py:1033-1035, one serial
-chain over the whole file), the cache, the backends and writing snapshots.  There is no CPU
+chain over the whole file), the cache and the backends; writing snapshots is
+replicat_amd/snapshot_write.py.  There is no CPU
 fallback for the device work: without the HIP library or a GPU, construction raises
 ``ChunkerUnavailable``.
 """
