@@ -176,6 +176,83 @@ int rc_snapshot_seal_tables_host(rc_snapshot *s, uint64_t n, const uint8_t *dige
 int rc_snapshot_write_timing_read(rc_snapshot *s, double *encode_ms, double *b64_ms, double *crypt_ms,
                                   uint64_t *encode_calls);
 
+/* ---------------------------------------------------------------------------------------------
+ * Writing `data`: the other array of a snapshot body that grows with the number of chunks.  Every
+ * file of body['data']['files'] lists its PARTS, one per chunk that touches it
+ * (replicat/repository.py:1374-1411):
+ *     {"path":..,"chunks":[{"range":[S,E],"index":I,"counter":C},...],"digest":..}
+ * The text of serialize(data) is m + 1 FIXED PIECES the host writes -- piece 0 from the opening
+ * brace to the '[' of the first file's list, piece j from behind the ']' of list j - 1 to the '['
+ * of list j, piece m the rest -- with the parts of file j, in counter order, between pieces j and
+ * j + 1.  A part's text is followed by ',' or, for the last of its file, ']'.  Three stages on the
+ * same handle, each enqueued on hip_stream without a synchronisation; all arrays are DEVICE memory
+ * unless said otherwise.  Kernels: replicat_amd/csrc/snapshot_data.hip.
+ *
+ * The stream: chunk k ends at d_chunk_ends[k] (strictly increasing; it starts where chunk k - 1
+ * ends, chunk 0 at 0), refers to slot d_table_index[k] of the table and has counter counter0 + k.
+ * File f, in the order of the listing, is the bytes d_file_start[f] .. d_file_end[f] of the stream.
+ * What the caller has checked (replicat_amd/snapshot_write.py raises ValueError; the device
+ * rejects nothing): the ends increase strictly; file_start does not decrease; file_end[f] >=
+ * file_start[f]; file_start[f + 1] >= file_end[f]; the last file_end <= the last chunk end; chunk
+ * lengths, n and counter0 + n - 1 are below 2^32.  Input outside these rules gives parts that mean
+ * nothing, and no access outside the arrays.
+ * ------------------------------------------------------------------------------------------- */
+
+/* A part record: RC_SNAPSHOT_PART_WORDS 32-bit words -- file, chunk, start, end, index, counter,
+ * and two words the later stages read (the length of the part's text, and its place among the
+ * texts of its workgroup of 256 parts). */
+#define RC_SNAPSHOT_PART_WORDS 8
+
+/* Host only: the bytes of {"range":[start,end],"index":index,"counter":counter} and the
+ * separator behind it: 34 and the decimal digits of the four numbers, 38 to 74. */
+uint32_t rc_snapshot_part_len_for(uint32_t start, uint32_t end, uint32_t index, uint32_t counter);
+
+/* Host only: the most parts n chunks and m files can have (n + 2 m; 0 when either is 0): the
+ * records the first stage needs room for. */
+uint64_t rc_snapshot_parts_capacity(uint64_t n, uint64_t m);
+
+/* Stage 1, parts.  d_part_first (m + 1 words of 64 bits): the parts of file f are the records
+ * d_part_first[f] .. d_part_first[f + 1] - 1, one per chunk from the first that touches the file
+ * (lower_bound(chunk_ends, file_start)) to the last (min(upper_bound(chunk_ends, file_end), n - 1)),
+ * with range [max(file_start - chunk_start, 0), min(file_end, chunk_end) - chunk_start]; so
+ * d_part_first[m] is their number.  d_records: room for rc_snapshot_parts_capacity(n, m) records,
+ * 16-byte aligned.  d_group_len: ceil(capacity / 256) + 1 words of 64 bits, the summed text
+ * lengths of every 256 parts, for stage 2.  d_scratch: 4 m bytes.  With n == 0 or m == 0 there
+ * are no parts: d_part_first is all zero.  RC_ERR_ARGUMENT: a NULL handle or array; n or m of
+ * 2^32 or more. */
+int rc_snapshot_parts_device(rc_snapshot *s, uint64_t n, const uint64_t *d_chunk_ends,
+                             const uint32_t *d_table_index, uint32_t counter0, uint64_t m,
+                             const uint64_t *d_file_start, const uint64_t *d_file_end,
+                             uint64_t *d_part_first, uint32_t *d_records, uint64_t *d_group_len,
+                             void *d_scratch, void *hip_stream);
+
+/* Stage 2, lengths: where everything goes in the text.  d_group_len turns, in place, into the
+ * exclusive prefix of its ceil(capacity / 256) sums (the sum itself in the word behind them), and
+ * so does d_piece_len, the lengths of the m + 1 fixed pieces (m + 2 words; the sum in the last).
+ * d_piece_off[j], j <= m: the offset of piece j in the text.  *d_total: the length of the text --
+ * the one device result a file's layout waits for.  n and m are stage 1's. */
+int rc_snapshot_data_len_device(rc_snapshot *s, uint64_t n, uint64_t m, const uint64_t *d_part_first,
+                                const uint32_t *d_records, uint64_t *d_group_len,
+                                uint64_t *d_piece_len, uint64_t *d_piece_off, uint64_t *d_total,
+                                void *hip_stream);
+
+/* Stage 3, text: every part's text at its offset from d_text (any alignment), and with d_pieces
+ * -- the fixed pieces packed back to back, as stage 2 saw their lengths -- the pieces at theirs:
+ * exactly *d_total bytes from d_text.  With d_pieces NULL only the parts are written: the bytes of
+ * the pieces, like those before and after the text, are not touched.  The other arrays are as
+ * stage 2 left them. */
+int rc_snapshot_encode_data_device(rc_snapshot *s, uint64_t n, uint64_t m, const uint64_t *d_part_first,
+                                   const uint32_t *d_records, const uint64_t *d_group_off,
+                                   const uint64_t *d_piece_pre, const uint64_t *d_piece_off,
+                                   const uint8_t *d_pieces, uint8_t *d_text, void *hip_stream);
+
+/* The three stages in the kernel timing rc_snapshot_timing_enable switches on: the summed
+ * milliseconds of the count, scan and record kernels of stage 1 (parts_ms), of the scans and the
+ * piece offsets of stage 2 (scan_ms), of the text and piece kernels of stage 3 (encode_ms, and
+ * their number of calls in encode_calls); clears them. */
+int rc_snapshot_data_timing_read(rc_snapshot *s, double *parts_ms, double *scan_ms, double *encode_ms,
+                                 uint64_t *encode_calls);
+
 #ifdef __cplusplus
 }
 #endif

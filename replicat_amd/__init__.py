@@ -11,7 +11,7 @@ __version__ = '0.3.0'
 
 _GC_EXPORTS = ('GpuChunkGC', 'CleanPlan')
 _SNAPSHOTS_EXPORTS = ('GpuSnapshotLoader', 'LoadedSnapshot')
-_SNAPSHOT_WRITE_EXPORTS = ('GpuSnapshotWriter', 'WrittenSnapshot', 'DeviceDigests')
+_SNAPSHOT_WRITE_EXPORTS = ('GpuSnapshotWriter', 'WrittenSnapshot', 'DeviceDigests', 'SnapshotLayout', 'SnapshotData')
 __all__ = list(_GC_EXPORTS + _SNAPSHOTS_EXPORTS + _SNAPSHOT_WRITE_EXPORTS)
 
 

@@ -192,6 +192,13 @@ SIGNATURES = {
     'rc_snapshot_seal_tables_host': (_int, [_p, _u64, _p, _p, _p, _p, _p]),
     'rc_snapshot_write_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                              ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
+    'rc_snapshot_part_len_for': (_u32, [_u32, _u32, _u32, _u32]),
+    'rc_snapshot_parts_capacity': (_u64, [_u64, _u64]),
+    'rc_snapshot_parts_device': (_int, [_p, _u64, _p, _p, _u32, _u64, _p, _p, _p, _p, _p, _p, _p]),
+    'rc_snapshot_data_len_device': (_int, [_p, _u64, _u64, _p, _p, _p, _p, _p, _p, _p]),
+    'rc_snapshot_encode_data_device': (_int, [_p, _u64, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'rc_snapshot_data_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
 }
 
 

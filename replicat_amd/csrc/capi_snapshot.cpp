@@ -16,6 +16,7 @@
 #include "capi_internal.h"
 #include "cipher_host.h"
 #include "digest_kernels.h"
+#include "gc_kernels.h"
 #include "restore_kernels.h"
 #include "snapshot_kernels.h"
 
@@ -40,6 +41,8 @@ struct rc_snapshot {
     // writing (snapshot_write.hip)
     rc::DevBuf d_nonces;  // blocking host path: the nonces of one call
     rc::PairTimer t_encode, t_b64_encode, t_seal;
+    // writing `data` (snapshot_data.hip)
+    rc::PairTimer t_parts, t_scan, t_data;
 };
 
 namespace {
@@ -299,7 +302,8 @@ void rc_snapshot_destroy(rc_snapshot *s) {
             w.d_scratch.release();
         });
         for (rc::DevBuf *b : {&s->d_kdf, &s->d_in, &s->d_out, &s->d_meta, &s->d_slots, &s->d_nonces}) b->release();
-        for (rc::PairTimer *t : {&s->t_crypt, &s->t_decode, &s->t_b64, &s->t_encode, &s->t_b64_encode, &s->t_seal})
+        for (rc::PairTimer *t : {&s->t_crypt, &s->t_decode, &s->t_b64, &s->t_encode, &s->t_b64_encode, &s->t_seal,
+                                 &s->t_parts, &s->t_scan, &s->t_data})
             t->release();
     });
     delete s;
@@ -424,7 +428,8 @@ int rc_snapshot_b64_device(rc_snapshot *s, uint64_t n, const uint8_t *const *d_t
 
 int rc_snapshot_timing_enable(rc_snapshot *s, int enable) {
     if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
-    return rc::timing_enable(s, {&s->t_crypt, &s->t_decode, &s->t_b64, &s->t_encode, &s->t_b64_encode, &s->t_seal},
+    return rc::timing_enable(s, {&s->t_crypt, &s->t_decode, &s->t_b64, &s->t_encode, &s->t_b64_encode, &s->t_seal,
+                                 &s->t_parts, &s->t_scan, &s->t_data},
                              enable);
 }
 
@@ -577,6 +582,95 @@ int rc_snapshot_write_timing_read(rc_snapshot *s, double *encode_ms, double *b64
     if (int rc = s->t_seal.read(crypt_ms, nullptr)) return rc;
     if (int rc = s->t_b64_encode.read(b64_ms, nullptr)) return rc;
     return s->t_encode.read(encode_ms, encode_calls);
+}
+
+// ------------------------------------------------------------------------------- writing `data`
+
+uint32_t rc_snapshot_part_len_for(uint32_t start, uint32_t end, uint32_t index, uint32_t counter) {
+    return rc_snap_part_len(start, end, index, counter);
+}
+
+uint64_t rc_snapshot_parts_capacity(uint64_t n, uint64_t m) { return rc_snap_part_capacity(n, m); }
+
+int rc_snapshot_parts_device(rc_snapshot *s, uint64_t n, const uint64_t *d_chunk_ends, const uint32_t *d_table_index,
+                             uint32_t counter0, uint64_t m, const uint64_t *d_file_start, const uint64_t *d_file_end,
+                             uint64_t *d_part_first, uint32_t *d_records, uint64_t *d_group_len, void *d_scratch,
+                             void *hip_stream) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    if (n > 0xFFFFFFFFull || m > 0xFFFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "2^32 or more chunks or files");
+    if (!d_part_first || !d_group_len) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    const uint64_t capacity = rc_snap_part_capacity(n, m);
+    if (capacity && (!d_chunk_ends || !d_table_index || !d_file_start || !d_file_end || !d_records || !d_scratch))
+        return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    if (reinterpret_cast<uintptr_t>(d_records) & 15) return rc_fail(RC_ERR_ALIGN, "d_records is not 16-byte aligned");
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    if (!capacity) {
+        RC_HIP_TRY(hipMemsetAsync(d_part_first, 0, (m + 1) * sizeof(uint64_t), st));
+        RC_HIP_TRY(hipMemsetAsync(d_group_len, 0, sizeof(uint64_t), st));
+        return RC_OK;
+    }
+    uint32_t *d_lo = static_cast<uint32_t *>(d_scratch);
+    return rc::timed(s->t_parts, st, [&] {
+        if (int rc = rc_snap_launch_part_count(d_chunk_ends, n, d_file_start, d_file_end, m, d_part_first, d_lo, st))
+            return rc;
+        if (int rc = rc_gc_launch_scan(d_part_first, m, d_part_first + m, st)) return rc;
+        return rc_snap_launch_part_records(d_chunk_ends, d_table_index, counter0, d_file_start, d_file_end, m,
+                                           d_part_first, d_lo, capacity, d_records, d_group_len, st);
+    });
+}
+
+int rc_snapshot_data_len_device(rc_snapshot *s, uint64_t n, uint64_t m, const uint64_t *d_part_first,
+                                const uint32_t *d_records, uint64_t *d_group_len, uint64_t *d_piece_len,
+                                uint64_t *d_piece_off, uint64_t *d_total, void *hip_stream) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    if (n > 0xFFFFFFFFull || m > 0xFFFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "2^32 or more chunks or files");
+    const uint64_t capacity = rc_snap_part_capacity(n, m);
+    if (!d_part_first || !d_group_len || !d_piece_len || !d_piece_off || !d_total || (capacity && !d_records))
+        return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const uint64_t groups = rc_snap_part_groups(capacity);
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    return rc::timed(s->t_scan, st, [&] {
+        if (int rc = rc_gc_launch_scan(d_group_len, groups, d_group_len + groups, st)) return rc;
+        if (int rc = rc_gc_launch_scan(d_piece_len, m + 1, d_piece_len + m + 1, st)) return rc;
+        return rc_snap_launch_piece_offsets(d_part_first, m, d_records, capacity, d_group_len, d_piece_len,
+                                            d_piece_off, d_total, st);
+    });
+}
+
+int rc_snapshot_encode_data_device(rc_snapshot *s, uint64_t n, uint64_t m, const uint64_t *d_part_first,
+                                   const uint32_t *d_records, const uint64_t *d_group_off, const uint64_t *d_piece_pre,
+                                   const uint64_t *d_piece_off, const uint8_t *d_pieces, uint8_t *d_text,
+                                   void *hip_stream) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    if (n > 0xFFFFFFFFull || m > 0xFFFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "2^32 or more chunks or files");
+    const uint64_t capacity = rc_snap_part_capacity(n, m);
+    if (!d_part_first || !d_group_off || !d_piece_pre || !d_text || (capacity && !d_records) ||
+        (d_pieces && !d_piece_off))
+        return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    return rc::timed(s->t_data, st, [&] {
+        if (int rc = rc_snap_launch_encode_data(d_records, d_part_first + m, capacity, d_group_off, d_piece_pre, d_text,
+                                                st))
+            return rc;
+        if (!d_pieces) return 0;
+        return rc_snap_launch_place_pieces(d_pieces, d_piece_pre, d_piece_off, m + 1, d_text, st);
+    });
+}
+
+int rc_snapshot_data_timing_read(rc_snapshot *s, double *parts_ms, double *scan_ms, double *encode_ms,
+                                 uint64_t *encode_calls) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    if (int rc = s->t_parts.read(parts_ms, nullptr)) return rc;
+    if (int rc = s->t_scan.read(scan_ms, nullptr)) return rc;
+    return s->t_data.read(encode_ms, encode_calls);
 }
 
 }  // extern "C"

@@ -211,6 +211,11 @@ int rc_gc_launch_sweep(const IndexView &v, const rc_blake2b_state *d_mac, uint64
     return rc::launch_status("rc_gc_sweep_kernel");
 }
 
+int rc_gc_launch_scan(uint64_t *d_counts, uint64_t m, uint64_t *d_total, hipStream_t st) {
+    rc_gc_scan_kernel<<<1, 1024, 0, st>>>(d_counts, m, d_total);
+    return rc::launch_status("rc_gc_scan_kernel");
+}
+
 int rc_gc_launch_compact(const uint8_t *d_flags, uint64_t n, uint8_t want, uint64_t index_base,
                          uint64_t *d_scratch, uint64_t *d_out, uint64_t *d_total, hipStream_t st) {
     const unsigned groups = static_cast<unsigned>(rc_gc_groups(n));
@@ -218,8 +223,7 @@ int rc_gc_launch_compact(const uint8_t *d_flags, uint64_t n, uint8_t want, uint6
         rc_gc_count_kernel<<<groups, kGcThreads, 0, st>>>(d_flags, n, want, d_scratch);
         if (int rc = rc::launch_status("rc_gc_count_kernel")) return rc;
     }
-    rc_gc_scan_kernel<<<1, 1024, 0, st>>>(d_scratch, groups, d_total);
-    if (int rc = rc::launch_status("rc_gc_scan_kernel")) return rc;
+    if (int rc = rc_gc_launch_scan(d_scratch, groups, d_total, st)) return rc;
     if (groups) {
         rc_gc_scatter_kernel<<<groups, kGcThreads, 0, st>>>(d_flags, n, want, d_scratch, index_base, d_out);
         if (int rc = rc::launch_status("rc_gc_scatter_kernel")) return rc;

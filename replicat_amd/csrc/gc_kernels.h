@@ -31,6 +31,11 @@ int rc_gc_launch_sweep(const IndexView &v, const rc_blake2b_state *d_mac, uint64
                        const uint8_t *d_names, const uint8_t *d_tags, uint8_t *d_verdict,
                        hipStream_t st);
 
+// The scan of the compaction, for every family that counts, scans and scatters (snapshot_data.hip):
+// d_counts[0 .. m) becomes its exclusive prefix in place, and d_counts[m] and *d_total the sum
+// (d_total may be d_counts + m).  One workgroup; m == 0 writes the two zeros.
+int rc_gc_launch_scan(uint64_t *d_counts, uint64_t m, uint64_t *d_total, hipStream_t st);
+
 // Stable compaction: d_out[0 .. *d_total) = index_base + i for the i < n with d_flags[i] == want,
 // ascending.  Three launches (workgroup counts, their scan, the scatter); d_scratch holds
 // rc_gc_scratch_words(n) words.  n == 0 writes *d_total = 0.

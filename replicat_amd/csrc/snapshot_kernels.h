@@ -58,3 +58,50 @@ int rc_snap_launch_encode_tables(const SnapTable *d_tables, const SnapBlock *d_b
 // Exactly 4 ceil(len / 3) characters at each text's out.
 int rc_snap_launch_b64_encode(const SnapText *d_texts, const SnapBlock *d_blocks, uint64_t n_blocks,
                               hipStream_t stream);
+
+// snapshot_data.hip: the parts of the files of a snapshot and their text inside `data`.  A part is
+// RC_SNAPSHOT_PART_WORDS words: file, chunk, start, end, index, counter, then the length of its
+// text {"range":[S,E],"index":I,"counter":C} with the ',' or ']' behind it, then rel: the summed
+// lengths of the parts before it in its workgroup of kSnapThreads (low 16 bits), and in the top bit
+// whether it is the last part of its file.
+constexpr uint32_t kSnapPartWords = RC_SNAPSHOT_PART_WORDS;
+constexpr uint32_t kSnapPartFixed = 34;   // everything of a part's text but the digits
+constexpr uint32_t kSnapPartMaxLen = 74;  // four numbers of ten digits
+
+__host__ __device__ inline uint32_t rc_snap_digits(uint32_t v) {
+    return 1u + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u) + (v >= 100000u) + (v >= 1000000u) +
+           (v >= 10000000u) + (v >= 100000000u) + (v >= 1000000000u);
+}
+__host__ __device__ inline uint32_t rc_snap_part_len(uint32_t start, uint32_t end, uint32_t index, uint32_t counter) {
+    return kSnapPartFixed + rc_snap_digits(start) + rc_snap_digits(end) + rc_snap_digits(index) + rc_snap_digits(counter);
+}
+
+// A file has a part in every chunk it touches, and two neighbouring files share at most two
+// chunks: n chunks and m files have at most n + 2 m parts, in rc_snap_part_groups workgroups.
+inline uint64_t rc_snap_part_capacity(uint64_t n, uint64_t m) { return n && m ? n + 2 * m : 0; }
+inline uint64_t rc_snap_part_groups(uint64_t capacity) { return (capacity + kSnapThreads - 1) / kSnapThreads; }
+
+// d_counts[f] = the parts of file f, d_lo[f] = the first chunk that touches it (n >= 1).
+int rc_snap_launch_part_count(const uint64_t *d_ends, uint64_t n, const uint64_t *d_file_start,
+                              const uint64_t *d_file_end, uint64_t m, uint64_t *d_counts, uint32_t *d_lo,
+                              hipStream_t st);
+// The parts d_part_first[m] (at most `capacity`) as records in file order, and per workgroup of
+// parts the summed length of their text (all rc_snap_part_groups(capacity) words are written).
+int rc_snap_launch_part_records(const uint64_t *d_ends, const uint32_t *d_table_index, uint32_t counter0,
+                                const uint64_t *d_file_start, const uint64_t *d_file_end, uint64_t m,
+                                const uint64_t *d_part_first, const uint32_t *d_lo, uint64_t capacity,
+                                uint32_t *d_records, uint64_t *d_group_len, hipStream_t st);
+// d_piece_off[j], j <= m: where fixed piece j starts in the text -- behind the pieces before it
+// (d_piece_pre: the exclusive prefix of the m + 1 lengths, the sum at [m + 1]) and the parts of the
+// files before it (d_group_off: the exclusive prefix of the workgroup sums, the sum at [groups]);
+// *d_total = the length of the whole text.
+int rc_snap_launch_piece_offsets(const uint64_t *d_part_first, uint64_t m, const uint32_t *d_records,
+                                 uint64_t capacity, const uint64_t *d_group_off, const uint64_t *d_piece_pre,
+                                 uint64_t *d_piece_off, uint64_t *d_total, hipStream_t st);
+// The text of every part at its place in d_text, and no other byte.
+int rc_snap_launch_encode_data(const uint32_t *d_records, const uint64_t *d_part_total, uint64_t capacity,
+                               const uint64_t *d_group_off, const uint64_t *d_piece_pre, uint8_t *d_text,
+                               hipStream_t st);
+// The `count` packed pieces at their offsets in d_text.
+int rc_snap_launch_place_pieces(const uint8_t *d_pieces, const uint64_t *d_piece_pre, const uint64_t *d_piece_off,
+                                uint64_t count, uint8_t *d_text, hipStream_t st);

@@ -247,6 +247,19 @@ class SnapshotStream:
                 d['digest'] = f.digest
         return out
 
+    def layout(self):
+        """The same run as arrays (``snapshot_write.SnapshotLayout``): the cuts, the table indices
+        and the bounds, paths and digests of the files, with no object per part -- what
+        ``GpuSnapshotWriter`` takes, inside a ``SnapshotData``, in place of ``snapshot_files()``."""
+        from .snapshot_write import SnapshotLayout  # imports this module
+        n, m = len(self.chunks), len(self.files)
+        return SnapshotLayout(
+            chunk_ends=np.fromiter((c.stream_end for c in self.chunks), dtype=np.uint64, count=n),
+            table_index=np.fromiter((c.table_index for c in self.chunks), dtype=np.uint32, count=n),
+            file_starts=np.fromiter((f.stream_start for f in self.files), dtype=np.uint64, count=m),
+            file_ends=np.fromiter((f.stream_end for f in self.files), dtype=np.uint64, count=m),
+            paths=[f.path for f in self.files], digests=[f.digest for f in self.files])
+
 
 def _fstat_size(record, src):
     try:

@@ -10,7 +10,9 @@ What it replaces, in replicat's repository.py: ``_encrypt_snapshot_body`` (:982-
     serialized = serialize({'chunks': chunks, 'data': encrypted_private_data})
     digest = hash_digest(serialized); name, tag = digest.hex(), mac(digest).hex()
 
-``GpuSnapshotWriter.write`` serialises ``data`` -- irregular JSON -- on the host, encrypts it under
+``GpuSnapshotWriter.write`` serialises a ``data`` dict -- irregular JSON -- on the host (or, given
+a ``SnapshotData``, writes the part records of its files on the device between per-file text the
+host supplies: include/replicat_snapshot.h, "Writing `data`"), encrypts it under
 the user key on the device, hashes the result there (or, when it is long, on host threads:
 ``DeviceSnapshotProducer.HOST_DIGEST_MIN_BY_HASH``, the loader's rule), encodes the table text from
 the 64-byte digest slots, derives the subkey and seals the table (``rc_snapshot_seal_tables_device``),
@@ -22,8 +24,7 @@ An unencrypted file is ``{"chunks":`` + table text + ``,"data":`` + ``serialize(
 What the writer emits is canonical for ``GpuSnapshotLoader``'s strict decoders: the loader reads
 it back with no host fallback.
 
-Out of scope: uploading the file to a backend, the cache, and building ``data`` from
-``SnapshotStream.snapshot_files()`` (the caller's one-liner).  There is no CPU fallback for the
+Out of scope: uploading the file to a backend and the cache.  There is no CPU fallback for the
 device work: without the HIP library or a GPU, construction raises ``ChunkerUnavailable``.
 """
 import base64
@@ -33,7 +34,7 @@ import json
 import os
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
-from typing import Any, Callable, Iterable, List, NamedTuple, Optional, Tuple
+from typing import Any, Callable, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -75,6 +76,115 @@ def assemble_plain(table_text, data_text) -> bytes:
 
 def b64_len(nbytes: int) -> int:
     return 4 * ((nbytes + 2) // 3)
+
+
+@dataclass
+class SnapshotLayout:
+    """Where the chunks and the files of one snapshot lie in its stream, as arrays: chunk k ends at
+    ``chunk_ends[k]`` (it starts where chunk k - 1 ends, chunk 0 at 0) and refers to slot
+    ``table_index[k]`` of the table; file f is the bytes ``file_starts[f] .. file_ends[f]``, has
+    ``paths[f]``, ``digests[f]`` (bytes or None) and, when ``metadata`` is given, ``metadata[f]``.
+    ``SnapshotStream.layout()`` builds one from a producer's records."""
+    chunk_ends: Any
+    table_index: Any
+    file_starts: Any
+    file_ends: Any
+    paths: Sequence[str]
+    digests: Sequence[Optional[bytes]]
+    metadata: Optional[Sequence[Any]] = None
+
+    def __post_init__(self):
+        self.chunk_ends = _array(self.chunk_ends, np.uint64, 'chunk_ends')
+        self.table_index = _array(self.table_index, np.uint32, 'table_index')
+        self.file_starts = _array(self.file_starts, np.uint64, 'file_starts')
+        self.file_ends = _array(self.file_ends, np.uint64, 'file_ends')
+
+    @property
+    def n(self) -> int:
+        return int(self.chunk_ends.size)
+
+    @property
+    def m(self) -> int:
+        return int(self.file_starts.size)
+
+    def validate(self, counter0: int = 1):
+        """ValueError unless the arrays are what the device stages take for granted
+        (include/replicat_snapshot.h, "Writing `data`"): nothing is left for the device to reject."""
+        n, m = self.n, self.m
+        ends, fs, fe = self.chunk_ends, self.file_starts, self.file_ends
+        if self.table_index.size != n:
+            raise ValueError(f'{n} chunk ends and {self.table_index.size} table indices')
+        if not (fe.size == len(self.paths) == len(self.digests) == m):
+            raise ValueError('file_starts, file_ends, paths and digests differ in length')
+        if self.metadata is not None and len(self.metadata) != m:
+            raise ValueError('metadata and paths differ in length')
+        if not 0 <= int(counter0) < 1 << 32 or n >= 1 << 32 or m >= 1 << 32 or (n and int(counter0) + n - 1 >= 1 << 32):
+            raise ValueError('the number of chunks, of files and the last counter must be below 2^32')
+        if n:
+            if n > 1 and not (ends[1:] > ends[:-1]).all():
+                raise ValueError('chunk_ends must be strictly increasing')
+            lengths = np.diff(ends, prepend=np.uint64(0))
+            if int(ends[0]) == 0 or int(lengths.max()) >= 1 << 32:
+                raise ValueError('every chunk must have between 1 and 2^32 - 1 bytes')
+        if m:
+            if m > 1 and not (fs[1:] >= fs[:-1]).all():
+                raise ValueError('file_starts must not decrease')
+            if not (fe >= fs).all():
+                raise ValueError('a file ends before it starts')
+            if m > 1 and not (fs[1:] >= fe[:-1]).all():
+                raise ValueError('a file starts before the one in front of it ends')
+            if n and int(fe[-1]) > int(ends[-1]):
+                raise ValueError('the last file ends behind the last chunk')
+
+    def listing(self) -> np.ndarray:
+        """The files in the order ``files`` lists them, as indices: a file appears when the first
+        chunk that touches it is done, and the files one chunk touches are walked from the last
+        backwards (repository.py:1376-1391).  Without a chunk no file is listed."""
+        if self.n == 0 or self.m == 0:
+            return np.zeros(0, dtype=np.int64)
+        lo = np.searchsorted(self.chunk_ends, self.file_starts, side='left')
+        return np.lexsort((-np.arange(self.m, dtype=np.int64), lo))
+
+
+def _array(values, dtype, name) -> np.ndarray:
+    a = np.asarray(values)
+    if a.ndim != 1:
+        raise ValueError(f'{name} must be one-dimensional')
+    if a.size and a.dtype != dtype:
+        if a.dtype.kind not in 'iu' or int(a.min()) < 0 or int(a.max()) > np.iinfo(dtype).max:
+            raise ValueError(f'{name} must hold integers that fit {np.dtype(dtype).name}')
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+@dataclass
+class SnapshotData:
+    """The ``data`` of a snapshot body whose ``files`` follow from a layout: what
+    ``{'utc_timestamp': utc_timestamp, 'files': [...], 'note': note}`` serialises to, with the part
+    records of every file written on the device.  Chunk k has counter ``counter0 + k``."""
+    layout: SnapshotLayout
+    utc_timestamp: str
+    note: Optional[str] = None
+    counter0: int = 1
+
+    def pieces(self, order) -> List[str]:
+        """The text of ``serialize(data)`` around the part records of the files ``order`` lists:
+        len(order) + 1 pieces; the parts of listed file j go between pieces j and j + 1."""
+        lay, quote = self.layout, json.encoder.encode_basestring_ascii
+        first = '{"utc_timestamp":' + quote(self.utc_timestamp) + ',"files":['
+        last = (',"note":' + quote(self.note) if self.note is not None else '') + '}'
+        if len(order) == 0:
+            return [first + ']' + last]
+        paths, digests, meta = lay.paths, lay.digests, lay.metadata
+        b64 = base64.standard_b64encode
+        heads = ['{"path":' + quote(paths[f]) + ',"chunks":[' for f in order]
+        tails = [',"digest":' + ('null' if digests[f] is None else '{"!b":"' + str(b64(digests[f]), 'ascii') + '"}')
+                 for f in order]
+        if meta is not None:
+            tails = [t + ',"metadata":' + str(serialize(meta[f]), 'ascii') for t, f in zip(tails, order)]
+        out = [first + heads[0]]
+        out += [t + '},' + h for t, h in zip(tails, heads[1:])]
+        out.append(tails[-1] + '}]' + last)
+        return out
 
 
 class DeviceDigests(NamedTuple):
@@ -149,7 +259,7 @@ class GpuSnapshotWriter:
         self._buf = _Buffers(torch, self.dev)
         self._pool = None
         self.stats = dict.fromkeys(('snapshots', 'bytes_uploaded', 'bytes_copied_back', 'data_digests_host',
-                                    'data_digests_device', 'file_digests_host', 'file_digests_device'), 0)
+                                    'data_digests_device', 'file_digests_host', 'file_digests_device', 'data_syncs'), 0)
 
     def close(self):
         """Release the native handles and the buffers (the object is unusable after)."""
@@ -191,6 +301,15 @@ class GpuSnapshotWriter:
         check(lib().rc_snapshot_write_timing_read(self._h, *(ctypes.byref(m) for m in ms), ctypes.byref(calls)))
         return {'encode_ms': ms[0].value, 'b64_ms': ms[1].value, 'crypt_ms': ms[2].value,
                 'encode_calls': calls.value}
+
+    def data_timing_read(self) -> dict:
+        """Summed kernel milliseconds of the three stages of `data` since the last read: parts,
+        scans and offsets, text."""
+        ms = [ctypes.c_double() for _ in range(3)]
+        calls = ctypes.c_uint64()
+        check(lib().rc_snapshot_data_timing_read(self._h, *(ctypes.byref(m) for m in ms), ctypes.byref(calls)))
+        return {'parts_ms': ms[0].value, 'scan_ms': ms[1].value, 'data_encode_ms': ms[2].value,
+                'data_encode_calls': calls.value}
 
     # ------------------------------------------------------------------------ helpers
 
@@ -236,12 +355,24 @@ class GpuSnapshotWriter:
     def write_many(self, items: Iterable[Tuple[Any, Any]], *, file_digests=True) -> List[WrittenSnapshot]:
         """Seal several ``(chunks, data)`` bodies with one set of launches; the result is in the
         order of ``items``.  With ``file_digests`` false the files are not hashed: ``digest`` is
-        None and ``name``, ``tag`` and ``location`` are empty (profiling)."""
+        None and ``name``, ``tag`` and ``location`` are empty (profiling).
+
+        ``data`` is a dict, serialised on the host, or a ``SnapshotData``, whose part records the
+        device writes.  The length of such a text is a device result the layout of the file waits
+        for: a call with at least one ``SnapshotData`` copies the lengths back and synchronises
+        once before anything else is enqueued (``stats['data_syncs']``), and with an injected
+        nonce rule, which is shown the text, copies the texts back before it encrypts them."""
         if not self._h:
             raise RuntimeError('GpuSnapshotWriter is closed')
-        prepared = [(self._rows(chunks), serialize(data)) for chunks, data in items]
+        items = list(items)
+        for _, data in items:  # refused before anything is enqueued
+            if isinstance(data, SnapshotData):
+                data.layout.validate(data.counter0)
+        prepared = [(self._rows(chunks), data if isinstance(data, SnapshotData) else serialize(data))
+                    for chunks, data in items]
         if not prepared:
             return []
+        prepared = self._plan_all(prepared)
         run = self._run_encrypted if self.encrypted else self._run_plain
         contents, digests = run(prepared, file_digests)
         out = []
@@ -253,6 +384,106 @@ class GpuSnapshotWriter:
             tag = (self.naming.mac(digest) if self.naming.keyed else digest).hex()
             out.append(WrittenSnapshot(name, tag, snapshot_location(name, tag), body, digest))
         self.stats['snapshots'] += len(out)
+        return out
+
+    # ------------------------------------------------------------------ `data` on the device
+
+    def _to_device(self, array):
+        signed = {'u8': np.int64, 'u4': np.int32}.get(array.dtype.str[1:])  # the same bits
+        t = self._torch.from_numpy(array if signed is None else array.view(signed)).to(self.dev)
+        self.stats['bytes_uploaded'] += array.nbytes
+        return t
+
+    def _stage_parts(self, lay, order, counter0):
+        """Stage 1 over the files `order` lists; the caller is on the writer's stream."""
+        torch, n, m = self._torch, lay.n, len(order)
+        cap = int(lib().rc_snapshot_parts_capacity(n, m))
+        groups = (cap + 255) // 256
+        p = _DataPlan()
+        p.n, p.m, p.capacity, p.groups = n, m, cap, groups
+        p.ends = self._to_device(lay.chunk_ends)
+        p.index = self._to_device(lay.table_index)
+        p.starts = self._to_device(np.ascontiguousarray(lay.file_starts[order]))
+        p.stops = self._to_device(np.ascontiguousarray(lay.file_ends[order]))
+        p.part_first = torch.empty(m + 1, dtype=torch.int64, device=self.dev)
+        p.records = torch.empty((max(cap, 1), 8), dtype=torch.int32, device=self.dev)
+        p.group = torch.empty(groups + 1, dtype=torch.int64, device=self.dev)
+        scratch = torch.empty(max(m, 1), dtype=torch.int32, device=self.dev)
+        check(lib().rc_snapshot_parts_device(self._h, n, p.ends.data_ptr(), p.index.data_ptr(), int(counter0), m,
+                                             p.starts.data_ptr(), p.stops.data_ptr(), p.part_first.data_ptr(),
+                                             p.records.data_ptr(), p.group.data_ptr(), scratch.data_ptr(),
+                                             self._stream.cuda_stream))
+        return p
+
+    def _stage_lengths(self, p, pieces):
+        """Stage 2: the fixed pieces go up packed with their lengths; the total comes back."""
+        torch = self._torch
+        lens = np.zeros(p.m + 2, dtype=np.uint64)
+        lens[:p.m + 1] = np.fromiter(map(len, pieces), dtype=np.uint64, count=p.m + 1)
+        packed = np.frombuffer(bytearray(''.join(pieces), 'ascii'), dtype=np.uint8)
+        p.piece_pre = self._to_device(lens)
+        p.pieces = self._to_device(packed)
+        p.piece_off = torch.empty(p.m + 1, dtype=torch.int64, device=self.dev)
+        p.total = torch.empty(1, dtype=torch.int64, device=self.dev)
+        p.h_total = torch.empty(1, dtype=torch.int64).pin_memory()
+        check(lib().rc_snapshot_data_len_device(self._h, p.n, p.m, p.part_first.data_ptr(), p.records.data_ptr(),
+                                                p.group.data_ptr(), p.piece_pre.data_ptr(), p.piece_off.data_ptr(),
+                                                p.total.data_ptr(), self._stream.cuda_stream))
+        p.h_total.copy_(p.total, non_blocking=True)
+        self.stats['bytes_copied_back'] += 8
+
+    def _encode_data(self, p, ptr, with_pieces=True):
+        """Stage 3: the text of plan `p` at device address `ptr`."""
+        check(lib().rc_snapshot_encode_data_device(self._h, p.n, p.m, p.part_first.data_ptr(), p.records.data_ptr(),
+                                                   p.group.data_ptr(), p.piece_pre.data_ptr(), p.piece_off.data_ptr(),
+                                                   p.pieces.data_ptr() if with_pieces else None, ptr,
+                                                   self._stream.cuda_stream))
+
+    def _plan_all(self, prepared):
+        """Stages 1 and 2 of every ``SnapshotData`` among the items, then the one synchronisation
+        that brings their lengths back.  A body without a chunk lists no file: its text is the
+        host's."""
+        plans = []
+        with self._torch.cuda.stream(self._stream):
+            for k, (rows, data) in enumerate(prepared):
+                if not isinstance(data, SnapshotData):
+                    continue
+                order = data.layout.listing()
+                pieces = data.pieces(order)
+                if len(order) == 0:
+                    prepared[k] = (rows, pieces[0].encode('ascii'))
+                    continue
+                plan = self._stage_parts(data.layout, order, data.counter0)
+                self._stage_lengths(plan, pieces)
+                prepared[k] = (rows, plan)
+                plans.append(plan)
+            if plans:
+                self._stream.synchronize()
+                self.stats['data_syncs'] += 1
+                for plan in plans:
+                    plan.length = int(plan.h_total[0])
+        return prepared
+
+    def parts(self, layout: SnapshotLayout, counter0: int = 1) -> dict:
+        """The parts of the files of `layout`, as stage 1 finds them: ``part_first`` (m + 1; the
+        parts of file f are the rows part_first[f] .. part_first[f + 1] - 1, in counter order) and,
+        per part, ``file``, ``chunk``, ``start``, ``end``, ``index`` and ``counter``."""
+        if not self._h:
+            raise RuntimeError('GpuSnapshotWriter is closed')
+        layout.validate(counter0)
+        names = ('file', 'chunk', 'start', 'end', 'index', 'counter')
+        if layout.n == 0 or layout.m == 0:
+            out = {name: np.zeros(0, dtype=np.uint32) for name in names}
+            out['part_first'] = np.zeros(layout.m + 1, dtype=np.uint64)
+            return out
+        with self._torch.cuda.stream(self._stream):
+            p = self._stage_parts(layout, np.arange(layout.m), counter0)
+            first = p.part_first.cpu().numpy().astype(np.uint64)
+            total = int(first[-1])
+            records = p.records[:total].cpu().numpy().view(np.uint32)
+        self.stats['bytes_copied_back'] += first.nbytes + records.nbytes
+        out = {name: np.ascontiguousarray(records[:, k]) for k, name in enumerate(names)}
+        out['part_first'] = first
         return out
 
     # ------------------------------------------------------------------- device stages
@@ -385,7 +616,7 @@ class GpuSnapshotWriter:
         with torch.cuda.stream(self._stream):
             bases, firsts, counts = self._slots(prepared, order)
             tlen = [self.table_len(counts[i]) for i in order]
-            lens = [len(_PLAIN_HEAD) + t + len(_PLAIN_MID) + len(prepared[i][1]) + 1 for t, i in zip(tlen, order)]
+            lens = [len(_PLAIN_HEAD) + t + len(_PLAIN_MID) + _text_len(prepared[i][1]) + 1 for t, i in zip(tlen, order)]
             offs, total = [], 0
             for ln in lens:
                 offs.append(total)
@@ -394,9 +625,14 @@ class GpuSnapshotWriter:
             fp = d_file.data_ptr()
             self._seal(order, bases, firsts, counts, 0, 0, [fp + o + len(_PLAIN_HEAD) for o in offs], None)
             pieces = []
-            for o, t, i in zip(offs, tlen, order):
+            for o, t, ln, i in zip(offs, tlen, lens, order):
                 pieces.append((o, _PLAIN_HEAD))
-                pieces.append((o + len(_PLAIN_HEAD) + t, _PLAIN_MID + prepared[i][1] + b'}'))
+                text = prepared[i][1]
+                if isinstance(text, _DataPlan):  # straight into the file image
+                    pieces += [(o + len(_PLAIN_HEAD) + t, _PLAIN_MID), (o + ln - 1, b'}')]
+                    self._encode_data(text, fp + o + len(_PLAIN_HEAD) + t + len(_PLAIN_MID))
+                else:
+                    pieces.append((o + len(_PLAIN_HEAD) + t, _PLAIN_MID + text + b'}'))
             self._place(d_file, pieces)
             small, h_fd = self._file_digests(d_file, offs, lens, file_digests)
             contents, digests = self._finish(d_file, offs, lens, total, small, h_fd, file_digests)
@@ -410,9 +646,10 @@ class GpuSnapshotWriter:
         n, nb, kb = len(prepared), self.cipher.nonce_bytes, self.cipher.key_bytes
         # device-given slots last; within each kind, the data hashed on the device first
         order = sorted(range(n), key=lambda i: (isinstance(prepared[i][0], DeviceDigests),
-                                                len(prepared[i][1]) + over >= self.host_digest_min))
+                                                _text_len(prepared[i][1]) + over >= self.host_digest_min))
         texts = [prepared[i][1] for i in order]
-        ylen = [len(t) + over for t in texts]
+        planned = [k for k, t in enumerate(texts) if isinstance(t, _DataPlan)]
+        ylen = [_text_len(t) + over for t in texts]
         on_host = [y >= self.host_digest_min for y in ylen]
         stream = self._stream.cuda_stream
         enc = self.encryption
@@ -427,19 +664,42 @@ class GpuSnapshotWriter:
             if self.nonces is None:
                 noise = os.urandom(2 * nb * n)
                 data_nonces, table_nonces = noise[:nb * n], noise[nb * n:]
-            else:
-                data_nonces = b''.join(self._nonce(self.nonces(t, self.userkey)) for t in texts)
+            else:  # the rule is shown the texts: those made on the device come back first (below)
+                data_nonces = (None if planned else
+                               b''.join(self._nonce(self.nonces(t, self.userkey)) for t in texts))
                 table_nonces = None
-            pieces = [(key_off, self.userkey), (dn_off, data_nonces)]
+            pieces = [(key_off, self.userkey)]
+            if data_nonces is not None:
+                pieces.append((dn_off, data_nonces))
             if table_nonces is not None:
                 pieces.append((tn_off, table_nonces))
             t_off = []
             for t in texts:
                 t_off.append(at)
-                pieces.append((at, t))
-                at += _up(len(t))
+                if not isinstance(t, _DataPlan):
+                    pieces.append((at, t))
+                at += _up(_text_len(t))
             d_up = self._pinned_to_device('up', pieces, at)
             up = d_up.data_ptr()
+            for k in planned:  # straight into the cipher's input
+                self._encode_data(texts[k], up + t_off[k])
+            dn_ptr = up + dn_off
+            if data_nonces is None:
+                size = sum(_up(texts[k].length) for k in planned)
+                h_dt = self._buf.get('h_dt', max(size, 16), pinned=True)
+                spans, a = {}, 0
+                for k in planned:
+                    ln = texts[k].length
+                    h_dt[a:a + ln].copy_(d_up[t_off[k]:t_off[k] + ln], non_blocking=True)
+                    spans[k] = (a, ln)
+                    a += _up(ln)
+                self.stats['bytes_copied_back'] += size
+                self._stream.synchronize()
+                dt = h_dt.numpy()
+                seen = [dt[spans[k][0]:spans[k][0] + spans[k][1]].tobytes() if k in spans else t
+                        for k, t in enumerate(texts)]
+                data_nonces = b''.join(self._nonce(self.nonces(t, self.userkey)) for t in seen)
+                dn_ptr = self._pinned_to_device('dn', [(0, data_nonces)], nb * n).data_ptr()
             # blobs, table texts: 16-aligned offsets each
             y_off, x_off, q = [], [], 0
             for y in ylen:
@@ -453,8 +713,8 @@ class GpuSnapshotWriter:
             d_dd = self._buf.get('d_dd', n * SLOT)
             bp = d_blob.data_ptr()
             # 1. data under the user key
-            self.cipher.encrypt_device([up + o for o in t_off], [len(t) for t in texts], [up + key_off] * n,
-                                       [up + dn_off + nb * k for k in range(n)], [bp + o for o in y_off], stream)
+            self.cipher.encrypt_device([up + o for o in t_off], [_text_len(t) for t in texts], [up + key_off] * n,
+                                       [dn_ptr + nb * k for k in range(n)], [bp + o for o in y_off], stream)
             # 2. hash_digest(encrypted data): runs of device-hashed items, then the host's
             k = 0
             while k < n:
@@ -559,6 +819,16 @@ class GpuSnapshotWriter:
         return text[:NONCE_PREFIX]
 
 
+class _DataPlan:
+    """One ``SnapshotData`` after stages 1 and 2: the device arrays stage 3 reads, and ``length``,
+    the bytes of its text."""
+    length = 0
+
+
+def _text_len(text) -> int:
+    return text.length if isinstance(text, _DataPlan) else len(text)
+
+
 class _Span:
     """A raw device range as ``__cuda_array_interface__`` (torch.as_tensor wraps it, no copy)."""
 
@@ -570,5 +840,5 @@ def _device_view(torch, ptr, nbytes, dev):
     return torch.as_tensor(_Span(ptr, nbytes), device=dev)
 
 
-__all__ = ['GpuSnapshotWriter', 'WrittenSnapshot', 'DeviceDigests', 'serialize', 'type_hint', 'assemble_encrypted',
+__all__ = ['GpuSnapshotWriter', 'WrittenSnapshot', 'DeviceDigests', 'SnapshotLayout', 'SnapshotData', 'serialize', 'type_hint', 'assemble_encrypted',
            'assemble_plain', 'b64_len', 'ChunkEncryption']
