@@ -253,6 +253,94 @@ int rc_snapshot_encode_data_device(rc_snapshot *s, uint64_t n, uint64_t m, const
 int rc_snapshot_data_timing_read(rc_snapshot *s, double *parts_ms, double *scan_ms, double *encode_ms,
                                  uint64_t *encode_calls);
 
+/* ---------------------------------------------------------------------------------------------
+ * Reading `data`: the way back, from the text of serialize(data) to the parts as arrays, for a
+ * batch of n texts per call (one call serves many small snapshots).  serialize escapes every quote
+ * inside a JSON string, so the ten bytes {"range":[ occur in the text only where a part starts and
+ * "chunks":[ only where a list starts.  The device accepts exactly the part text serialize writes
+ * (the literals, canonical decimals below 2^32, start <= end, every part of a list on the byte
+ * behind the ',' of the one before it, the first behind "chunks":[, the last before ']'); a text
+ * with anything else gets RC_PARTS_NOT_CANONICAL and its other results are unspecified.  Everything
+ * outside the parts is left to the host's JSON parser, which reads the STRIPPED text: the text with
+ * every list's parts taken out, "chunks":[] for every file.
+ *
+ * A RUN is the parts of one list.  Parts and runs of all texts of a call are numbered together, in
+ * the order of the texts: text i has the parts d_text_first[i] .. d_text_first[i + 1] - 1 and the
+ * runs d_text_run_first[i] .. d_text_run_first[i + 1] - 1.  The arrays per part and per run have
+ * room for `capacity` entries (and one more where a total follows), capacity = the sum of
+ * rc_snapshot_parts_room over the texts: a canonical text cannot hold more parts, and a text that
+ * does is not canonical (a record that finds no room is dropped, and its text says so).
+ * Four stages on the same handle, each enqueued on hip_stream without a synchronisation; all
+ * arrays are DEVICE memory unless said otherwise.  Kernels: replicat_amd/csrc/snapshot_parse.hip.
+ * ------------------------------------------------------------------------------------------- */
+
+#define RC_PARTS_OK 0
+#define RC_PARTS_NOT_CANONICAL 2 /* RC_TABLE_NOT_CANONICAL's value */
+
+/* Word 7 of a part record read back: run, start, end, index, counter, the offset of the part's
+ * text in its snapshot's text (words 5 and 6, low word first), flags. */
+#define RC_PART_FIRST 1u /* the first part of its list */
+#define RC_PART_LAST 2u  /* the last part of its list */
+
+/* The bytes per text of the descriptor array stage 1 fills and stages 2 and 4 read. */
+#define RC_SNAPSHOT_TEXT_DESC_BYTES 32
+
+/* Host only: the most parts a canonical text of text_len bytes holds, text_len / 38 + 1
+ * (rc_snapshot_part_len_for is at least 38). */
+uint64_t rc_snapshot_parts_room(uint64_t text_len);
+
+/* Stage 1, find.  d_texts[i] / text_lens[i] (HOST arrays): the texts, at any alignment; the
+ * kernels read whole aligned 16-byte granules that hold at least one byte of a text, and what
+ * those hold before the text's first byte or behind its last is never taken for text.  Fills
+ * d_desc (RC_SNAPSHOT_TEXT_DESC_BYTES n bytes, 16-byte aligned; the stripped text of text i will
+ * start at the sum of text_lens[0 .. i - 1], each rounded up to 16), d_text_first and
+ * d_text_run_first (n + 1 words of 64 bits each), words 0, 5, 6 and 7 of every part's record in
+ * d_records (capacity records, 16-byte aligned) and d_run_part_first[runs] = parts
+ * (capacity + 1 words).  RC_ERR_ARGUMENT: a NULL handle or array; a NULL text with a length; n of
+ * 2^32 or more. */
+int rc_snapshot_find_parts_device(rc_snapshot *s, uint64_t n, const uint8_t *const *d_texts,
+                                  const uint64_t *text_lens, void *d_desc, uint32_t *d_records,
+                                  uint64_t *d_text_first, uint64_t *d_text_run_first,
+                                  uint64_t *d_run_part_first, void *hip_stream);
+
+/* Stage 2, parse.  Words 1 to 4 of every record and RC_PART_LAST in word 7; per run r its first
+ * part d_run_part_first[r], the offset of that part's text d_run_off[r] and the offset of the ']'
+ * that ends the list d_run_end[r] (so the run's text has d_run_end[r] - d_run_off[r] bytes);
+ * d_status[i] (n bytes) = RC_PARTS_OK or RC_PARTS_NOT_CANONICAL.  capacity is stage 1's. */
+int rc_snapshot_parse_parts_device(rc_snapshot *s, uint64_t n, const void *d_desc, uint64_t capacity,
+                                   const uint64_t *d_text_first, const uint64_t *d_text_run_first,
+                                   uint32_t *d_records, uint64_t *d_run_off, uint64_t *d_run_end,
+                                   uint64_t *d_run_part_first, uint8_t *d_status, void *hip_stream);
+
+/* Stage 3, sums.  Per run: d_run_count[r] parts, d_run_size[r] = the sum of end - start, and
+ * d_run_sorted[r] (bytes) = 1 if its counters increase strictly in listed order; per text
+ * d_text_size[i]; per part d_position[p] = the sum of the sizes of the parts before it in its run
+ * (chunk_position of replicat/repository.py:1795-1811 when the run is sorted).  With d_order
+ * (capacity words of 64 bits: a permutation of 0 .. parts - 1 that keeps every run in place, the
+ * stable order by run and counter) "before" is meant in that order, and d_run_sorted is left
+ * alone.  d_scratch: capacity + capacity / 256 + 8 words of 64 bits. */
+int rc_snapshot_part_sums_device(rc_snapshot *s, uint64_t n, uint64_t capacity, const uint64_t *d_text_first,
+                                 const uint64_t *d_text_run_first, const uint32_t *d_records,
+                                 const uint64_t *d_run_part_first, const uint64_t *d_order,
+                                 uint64_t *d_position, uint64_t *d_run_count, uint64_t *d_run_size,
+                                 uint8_t *d_run_sorted, uint64_t *d_text_size, uint64_t *d_scratch,
+                                 void *hip_stream);
+
+/* Stage 4, strip.  For every text whose status is RC_PARTS_OK: the text with the parts of every
+ * run taken out (the '[' before a run and the ']' behind it now touch) at its place in d_out (see
+ * stage 1), its length in d_stripped_len[i] (n words; 0 for the other texts), and per run the
+ * position of its ']' in the stripped text, d_run_close[r].  d_scratch as in stage 3. */
+int rc_snapshot_strip_parts_device(rc_snapshot *s, uint64_t n, const void *d_desc, uint64_t capacity,
+                                   const uint64_t *d_text_run_first, const uint64_t *d_run_off,
+                                   const uint64_t *d_run_end, const uint8_t *d_status, uint8_t *d_out,
+                                   uint64_t *d_run_close, uint64_t *d_stripped_len, uint64_t *d_scratch,
+                                   void *hip_stream);
+
+/* The four stages in the kernel timing rc_snapshot_timing_enable switches on: the summed
+ * milliseconds of each stage's kernels, and the number of find calls; clears them. */
+int rc_snapshot_read_timing_read(rc_snapshot *s, double *find_ms, double *parse_ms, double *sums_ms,
+                                 double *strip_ms, uint64_t *find_calls);
+
 #ifdef __cplusplus
 }
 #endif

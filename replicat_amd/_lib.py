@@ -43,6 +43,10 @@ RC_HASH_BLAKE2B, RC_HASH_SHA2, RC_HASH_SHA3 = 0, 1, 2
 RC_CIPHER_NONE, RC_CIPHER_AES_GCM, RC_CIPHER_CHACHA20_POLY1305 = 0, 1, 2
 RC_CHUNK_OK, RC_CHUNK_BAD_TAG, RC_CHUNK_CORRUPT = 0, 1, 2
 RC_TABLE_OK, RC_TABLE_BAD_TAG, RC_TABLE_NOT_CANONICAL = 0, 1, 2
+RC_PARTS_OK, RC_PARTS_NOT_CANONICAL = 0, 2
+RC_PART_FIRST, RC_PART_LAST = 1, 2  # word 7 of a part record read back
+RC_SNAPSHOT_PART_WORDS = 8
+RC_SNAPSHOT_TEXT_DESC_BYTES = 32
 
 # every symbol include/replicat_chunker.h, replicat_digest.h, replicat_cipher.h,
 # replicat_restore.h, replicat_index.h, replicat_gc.h and replicat_snapshot.h declare:
@@ -199,6 +203,14 @@ SIGNATURES = {
     'rc_snapshot_encode_data_device': (_int, [_p, _u64, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
     'rc_snapshot_data_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
+    'rc_snapshot_parts_room': (_u64, [_u64]),
+    'rc_snapshot_find_parts_device': (_int, [_p, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'rc_snapshot_parse_parts_device': (_int, [_p, _u64, _p, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'rc_snapshot_part_sums_device': (_int, [_p, _u64, _u64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'rc_snapshot_strip_parts_device': (_int, [_p, _u64, _p, _u64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'rc_snapshot_read_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                            ctypes.POINTER(_u64)]),
 }
 
 

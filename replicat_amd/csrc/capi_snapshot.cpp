@@ -43,6 +43,8 @@ struct rc_snapshot {
     rc::PairTimer t_encode, t_b64_encode, t_seal;
     // writing `data` (snapshot_data.hip)
     rc::PairTimer t_parts, t_scan, t_data;
+    // reading `data` (snapshot_parse.hip)
+    rc::PairTimer t_find, t_parse, t_sums, t_strip;
 };
 
 namespace {
@@ -303,7 +305,8 @@ void rc_snapshot_destroy(rc_snapshot *s) {
         });
         for (rc::DevBuf *b : {&s->d_kdf, &s->d_in, &s->d_out, &s->d_meta, &s->d_slots, &s->d_nonces}) b->release();
         for (rc::PairTimer *t : {&s->t_crypt, &s->t_decode, &s->t_b64, &s->t_encode, &s->t_b64_encode, &s->t_seal,
-                                 &s->t_parts, &s->t_scan, &s->t_data})
+                                 &s->t_parts, &s->t_scan, &s->t_data, &s->t_find, &s->t_parse, &s->t_sums,
+                                 &s->t_strip})
             t->release();
     });
     delete s;
@@ -429,7 +432,8 @@ int rc_snapshot_b64_device(rc_snapshot *s, uint64_t n, const uint8_t *const *d_t
 int rc_snapshot_timing_enable(rc_snapshot *s, int enable) {
     if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
     return rc::timing_enable(s, {&s->t_crypt, &s->t_decode, &s->t_b64, &s->t_encode, &s->t_b64_encode, &s->t_seal,
-                                 &s->t_parts, &s->t_scan, &s->t_data},
+                                 &s->t_parts, &s->t_scan, &s->t_data, &s->t_find, &s->t_parse, &s->t_sums,
+                                 &s->t_strip},
                              enable);
 }
 
@@ -671,6 +675,166 @@ int rc_snapshot_data_timing_read(rc_snapshot *s, double *parts_ms, double *scan_
     if (int rc = s->t_parts.read(parts_ms, nullptr)) return rc;
     if (int rc = s->t_scan.read(scan_ms, nullptr)) return rc;
     return s->t_data.read(encode_ms, encode_calls);
+}
+
+// ------------------------------------------------------------------------------- reading `data`
+
+uint64_t rc_snapshot_parts_room(uint64_t text_len) { return rc_snap_parts_room(text_len); }
+
+int rc_snapshot_find_parts_device(rc_snapshot *s, uint64_t n, const uint8_t *const *d_texts, const uint64_t *text_lens,
+                                  void *d_desc, uint32_t *d_records, uint64_t *d_text_first,
+                                  uint64_t *d_text_run_first, uint64_t *d_run_part_first, void *hip_stream) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    if (n == 0) return RC_OK;
+    if (!d_texts || !text_lens || !d_desc || !d_records || !d_text_first || !d_text_run_first || !d_run_part_first)
+        return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    if (n > 0xFFFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "more than 2^32 texts in one call");
+    if ((reinterpret_cast<uintptr_t>(d_records) | reinterpret_cast<uintptr_t>(d_desc)) & 15)
+        return rc_fail(RC_ERR_ALIGN, "d_records or d_desc is not 16-byte aligned");
+    std::vector<SnapParseText> texts(n);
+    std::vector<SnapBlock> blocks;
+    uint64_t capacity = 0, out = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (text_lens[i] && !d_texts[i]) return rc_fail(RC_ERR_ARGUMENT, "text %llu: null pointer", (unsigned long long)i);
+        if (text_lens[i] > (uint64_t(1) << 43))
+            return rc_fail(RC_ERR_ARGUMENT, "text %llu: longer than 2^43 bytes", (unsigned long long)i);
+        const uint64_t ptr = reinterpret_cast<uint64_t>(d_texts[i]), room = rc_snap_parts_room(text_lens[i]);
+        texts[i] = SnapParseText{ptr, text_lens[i], out, room};
+        capacity += room;
+        out += up16(text_lens[i]);
+        // workgroups over the aligned granules that hold the text, at least one
+        const uint64_t span = text_lens[i] ? (ptr & 15) + text_lens[i] : 0;
+        const uint64_t nb = span ? (span + kSnapFindSpan - 1) / kSnapFindSpan : 1;
+        for (uint64_t b = 0; b < nb; ++b) blocks.push_back(SnapBlock{uint32_t(i), uint32_t(b)});
+    }
+    const uint64_t nb = blocks.size();
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    rc::SlotRing<rc_snapshot::Staging>::Slot *w = nullptr;
+    if (int rc = s->ring.acquire(w)) return rc;
+    // SnapParseText[n] | SnapBlock[]; the workgroup counts: parts[nb + 1] | first parts[nb + 1]
+    const size_t block_off = up16(n * sizeof(SnapParseText));
+    const size_t stage = block_off + nb * sizeof(SnapBlock);
+    if (int rc = w->h_stage.ensure(stage)) return rc;
+    if (int rc = w->d_stage.ensure(stage)) return rc;
+    if (int rc = w->d_scratch.ensure(2 * (nb + 1) * sizeof(uint64_t))) return rc;
+    uint8_t *h = static_cast<uint8_t *>(w->h_stage.p);
+    uint8_t *d = static_cast<uint8_t *>(w->d_stage.p);
+    std::memcpy(h, texts.data(), n * sizeof(SnapParseText));
+    std::memcpy(h + block_off, blocks.data(), nb * sizeof(SnapBlock));
+    RC_HIP_TRY(hipMemcpyAsync(d, h, stage, hipMemcpyHostToDevice, st));
+    RC_HIP_TRY(hipMemcpyAsync(d_desc, d, n * sizeof(SnapParseText), hipMemcpyDeviceToDevice, st));
+    const SnapParseText *dt = reinterpret_cast<const SnapParseText *>(d);
+    const SnapBlock *db = reinterpret_cast<const SnapBlock *>(d + block_off);
+    uint64_t *part_counts = static_cast<uint64_t *>(w->d_scratch.p), *first_counts = part_counts + nb + 1;
+    if (int rc = rc::timed(s->t_find, st, [&] {
+            if (int rc = rc_snap_launch_find(false, dt, n, db, nb, part_counts, first_counts, capacity, d_records,
+                                             d_text_first, d_text_run_first, d_run_part_first, st))
+                return rc;
+            if (int rc = rc_gc_launch_scan(part_counts, nb, part_counts + nb, st)) return rc;
+            if (int rc = rc_gc_launch_scan(first_counts, nb, first_counts + nb, st)) return rc;
+            return rc_snap_launch_find(true, dt, n, db, nb, part_counts, first_counts, capacity, d_records, d_text_first,
+                                       d_text_run_first, d_run_part_first, st);
+        }))
+        return rc;
+    return s->ring.finish(*w, st);
+}
+
+namespace {
+
+// capacity as stage 1 computed it cannot be checked here; what can: it is not absurd
+int check_capacity(uint64_t n, uint64_t capacity) {
+    if (n > 0xFFFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "more than 2^32 texts in one call");
+    if (capacity < n || capacity > (uint64_t(1) << 40))
+        return rc_fail(RC_ERR_ARGUMENT, "capacity %llu for %llu texts", (unsigned long long)capacity, (unsigned long long)n);
+    return 0;
+}
+
+}  // namespace
+
+int rc_snapshot_parse_parts_device(rc_snapshot *s, uint64_t n, const void *d_desc, uint64_t capacity,
+                                   const uint64_t *d_text_first, const uint64_t *d_text_run_first, uint32_t *d_records,
+                                   uint64_t *d_run_off, uint64_t *d_run_end, uint64_t *d_run_part_first,
+                                   uint8_t *d_status, void *hip_stream) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    if (n == 0) return RC_OK;
+    if (!d_desc || !d_text_first || !d_text_run_first || !d_records || !d_run_off || !d_run_end || !d_run_part_first ||
+        !d_status)
+        return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    if (int rc = check_capacity(n, capacity)) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    RC_HIP_TRY(hipMemsetAsync(d_status, RC_PARTS_OK, n, st));
+    return rc::timed(s->t_parse, st, [&] {
+        return rc_snap_launch_parse(static_cast<const SnapParseText *>(d_desc), n, d_text_first, d_text_run_first,
+                                    capacity, d_records, d_run_off, d_run_end, d_run_part_first, d_status, st);
+    });
+}
+
+int rc_snapshot_part_sums_device(rc_snapshot *s, uint64_t n, uint64_t capacity, const uint64_t *d_text_first,
+                                 const uint64_t *d_text_run_first, const uint32_t *d_records,
+                                 const uint64_t *d_run_part_first, const uint64_t *d_order, uint64_t *d_position,
+                                 uint64_t *d_run_count, uint64_t *d_run_size, uint8_t *d_run_sorted,
+                                 uint64_t *d_text_size, uint64_t *d_scratch, void *hip_stream) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    if (n == 0) return RC_OK;
+    if (!d_text_first || !d_text_run_first || !d_records || !d_run_part_first || !d_position || !d_run_count ||
+        !d_run_size || !d_run_sorted || !d_text_size || !d_scratch)
+        return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    if (int rc = check_capacity(n, capacity)) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const uint64_t groups = rc_snap_parse_groups(capacity);
+    uint64_t *d_excl = d_scratch, *d_group = d_scratch + capacity + 1;  // excl[capacity + 1] | group[groups + 1]
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    if (!d_order) RC_HIP_TRY(hipMemsetAsync(d_run_sorted, 1, capacity, st));
+    return rc::timed(s->t_sums, st, [&] {
+        if (int rc = rc_snap_launch_size_sums(d_records, d_order, d_text_first + n, capacity, d_group, d_excl, st))
+            return rc;
+        if (int rc = rc_gc_launch_scan(d_group, groups, d_group + groups, st)) return rc;
+        return rc_snap_launch_positions(d_records, d_order, d_text_first, d_text_run_first, n, capacity,
+                                        d_run_part_first, d_excl, d_group, d_position, d_run_count, d_run_size,
+                                        d_run_sorted, d_text_size, st);
+    });
+}
+
+int rc_snapshot_strip_parts_device(rc_snapshot *s, uint64_t n, const void *d_desc, uint64_t capacity,
+                                   const uint64_t *d_text_run_first, const uint64_t *d_run_off,
+                                   const uint64_t *d_run_end, const uint8_t *d_status, uint8_t *d_out,
+                                   uint64_t *d_run_close, uint64_t *d_stripped_len, uint64_t *d_scratch,
+                                   void *hip_stream) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    if (n == 0) return RC_OK;
+    if (!d_desc || !d_text_run_first || !d_run_off || !d_run_end || !d_status || !d_out || !d_run_close ||
+        !d_stripped_len || !d_scratch)
+        return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    if (int rc = check_capacity(n, capacity)) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const uint64_t groups = rc_snap_parse_groups(capacity);
+    uint64_t *d_local = d_scratch, *d_group = d_scratch + capacity + 1;  // local[capacity + 1] | group[groups + 1]
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    RC_HIP_TRY(hipMemsetAsync(d_stripped_len, 0, n * sizeof(uint64_t), st));
+    return rc::timed(s->t_strip, st, [&] {
+        if (int rc = rc_snap_launch_run_len(d_run_off, d_run_end, d_text_run_first + n, capacity, d_local, d_group, st))
+            return rc;
+        if (int rc = rc_gc_launch_scan(d_group, groups, d_group + groups, st)) return rc;
+        return rc_snap_launch_strip(static_cast<const SnapParseText *>(d_desc), n, d_text_run_first, capacity, d_run_off,
+                                    d_run_end, d_local, d_group, d_status, d_out, d_run_close, d_stripped_len, st);
+    });
+}
+
+int rc_snapshot_read_timing_read(rc_snapshot *s, double *find_ms, double *parse_ms, double *sums_ms, double *strip_ms,
+                                 uint64_t *find_calls) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    if (int rc = s->t_parse.read(parse_ms, nullptr)) return rc;
+    if (int rc = s->t_sums.read(sums_ms, nullptr)) return rc;
+    if (int rc = s->t_strip.read(strip_ms, nullptr)) return rc;
+    return s->t_find.read(find_ms, find_calls);
 }
 
 }  // extern "C"

@@ -105,3 +105,57 @@ int rc_snap_launch_encode_data(const uint32_t *d_records, const uint64_t *d_part
 // The `count` packed pieces at their offsets in d_text.
 int rc_snap_launch_place_pieces(const uint8_t *d_pieces, const uint64_t *d_piece_pre, const uint64_t *d_piece_off,
                                 uint64_t count, uint8_t *d_text, hipStream_t st);
+
+// snapshot_parse.hip: the parts read back from the text of `data`.  A part is then
+// RC_SNAPSHOT_PART_WORDS words: run (the ordinal of its list among the lists of the call), start,
+// end, index, counter, the offset of its text in its snapshot's text (two words, low first), flags.
+constexpr uint32_t kSnapPartMinLen = 38;  // four numbers of one digit, with the separator
+constexpr uint32_t kSnapPartFirst = RC_PART_FIRST, kSnapPartLast = RC_PART_LAST;
+constexpr uint32_t kSnapFindSpan = kSnapThreads * 16;  // bytes of global memory per workgroup of the find kernels
+
+// One text of a call: len bytes at ptr (any alignment); its stripped text goes `out` bytes into the
+// packed output.
+struct SnapParseText {
+    uint64_t ptr, len, out, room;
+};
+static_assert(sizeof(SnapParseText) == RC_SNAPSHOT_TEXT_DESC_BYTES, "the descriptor the stages share");
+
+inline uint64_t rc_snap_parts_room(uint64_t text_len) { return text_len / kSnapPartMinLen + 1; }
+// Workgroups of 256 over 0 .. capacity (one more than the items: the sum's own place).
+inline uint64_t rc_snap_parse_groups(uint64_t capacity) { return (capacity + 1 + kSnapThreads - 1) / kSnapThreads; }
+
+// The two passes of the find stage over the d_blocks workgroups (SnapBlock: the block-th run of 256
+// aligned granules of text `item`): scatter false writes the two counts of every workgroup; scatter
+// true reads their exclusive prefixes (the sums at [n_blocks]) and writes words 0, 5, 6 and 7 of
+// every part's record, d_text_first / d_text_run_first [0 .. n_texts] and the end of the last run
+// in d_run_part_first.  No record at or behind `capacity` is written.
+int rc_snap_launch_find(bool scatter, const SnapParseText *d_texts, uint64_t n_texts, const SnapBlock *d_blocks,
+                        uint64_t n_blocks, uint64_t *d_part_counts, uint64_t *d_first_counts, uint64_t capacity,
+                        uint32_t *d_records, uint64_t *d_text_first, uint64_t *d_text_run_first,
+                        uint64_t *d_run_part_first, hipStream_t st);
+// Words 1 to 4 and the last-flag of every record, the three arrays of every run, and
+// RC_PARTS_NOT_CANONICAL into d_status[i] (RC_PARTS_OK beforehand) of every text with a part that
+// is not what serialize writes.
+int rc_snap_launch_parse(const SnapParseText *d_texts, uint64_t n_texts, const uint64_t *d_text_first,
+                         const uint64_t *d_text_run_first, uint64_t capacity, uint32_t *d_records, uint64_t *d_run_off,
+                         uint64_t *d_run_end, uint64_t *d_run_part_first, uint8_t *d_status, hipStream_t st);
+// d_excl[k], k <= parts: the summed sizes of the parts before the k-th (in d_order, when given) in
+// its workgroup of 256; d_sums[b]: the summed sizes of workgroup b, for all rc_snap_parse_groups.
+int rc_snap_launch_size_sums(const uint32_t *d_records, const uint64_t *d_order, const uint64_t *d_part_total,
+                             uint64_t capacity, uint64_t *d_sums, uint64_t *d_excl, hipStream_t st);
+// With d_group_off the exclusive prefix of d_sums: positions, run and text sums; without d_order
+// also d_run_sorted[r] = 0 (1 beforehand) where a run's counters do not increase strictly.
+int rc_snap_launch_positions(const uint32_t *d_records, const uint64_t *d_order, const uint64_t *d_text_first,
+                             const uint64_t *d_text_run_first, uint64_t n_texts, uint64_t capacity,
+                             const uint64_t *d_run_part_first, const uint64_t *d_excl, const uint64_t *d_group_off,
+                             uint64_t *d_position, uint64_t *d_run_count, uint64_t *d_run_size, uint8_t *d_run_sorted,
+                             uint64_t *d_text_size, hipStream_t st);
+// The bytes of every run as the two levels of a prefix: d_local[r], r <= capacity, and d_sums[b].
+int rc_snap_launch_run_len(const uint64_t *d_run_off, const uint64_t *d_run_end, const uint64_t *d_run_total,
+                           uint64_t capacity, uint64_t *d_local, uint64_t *d_sums, hipStream_t st);
+// The fixed pieces of every text whose status is RC_PARTS_OK at its place in d_out, d_run_close[r]
+// and d_stripped_len[i] (0 beforehand).
+int rc_snap_launch_strip(const SnapParseText *d_texts, uint64_t n_texts, const uint64_t *d_text_run_first,
+                         uint64_t capacity, const uint64_t *d_run_off, const uint64_t *d_run_end,
+                         const uint64_t *d_run_local, const uint64_t *d_run_group_off, const uint8_t *d_status,
+                         uint8_t *d_out, uint64_t *d_run_close, uint64_t *d_stripped_len, hipStream_t st);

@@ -90,6 +90,16 @@ class GpuChunkIndex:
                                             fresh_ptr, stream or None))
         return base.value
 
+    def resolve_names(self, n, names_ptr, owner_ptr, fresh_ptr, stream=0) -> int:
+        """Enqueue rc_index_resolve_names_device for ``n`` names in 64-byte slots at names_ptr
+        (device): owner (int64) and fresh (uint8) per name come back at owner_ptr / fresh_ptr.
+        Returns the call's id_base (name i has id id_base + i); grows the index as needed."""
+        self.ensure_room(n)
+        base = ctypes.c_uint64()
+        check(lib().rc_index_resolve_names_device(self._handle(), int(n), names_ptr, ctypes.byref(base), owner_ptr,
+                                                  fresh_ptr, stream or None))
+        return base.value
+
     @staticmethod
     def check_owners(owners):
         """Raise if a lookup exhausted its probe bound (owner -1): the table was full, which the

@@ -20,6 +20,7 @@ construction raises ``ChunkerUnavailable``.
 import ctypes
 import os
 import re
+from collections.abc import Mapping
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
@@ -87,6 +88,196 @@ def plan_restore(snapshots, file_regex=None) -> RestorePlan:
                 position += end - start
             plan.files[path] = position
     return plan
+
+
+class _ReferencesView(Mapping):
+    """``RestorePlanArrays.chunks_references``: the mapping ``plan_restore`` builds, read out of
+    the arrays.  One digest's list of ``(path, size, position, start)`` tuples is built when it is
+    asked for; iteration goes in the order of the reference's dict."""
+
+    def __init__(self, plan):
+        self._plan, self._slot = plan, None
+
+    def __len__(self):
+        return len(self._plan.digests)
+
+    def _digest(self, g) -> bytes:
+        return self._plan.digests[g].tobytes()
+
+    def _references(self, g) -> List[Reference]:
+        p = self._plan
+        a, b = int(p.ref_first[g]), int(p.ref_first[g + 1])
+        paths = p.paths
+        return [(paths[f], size, position, start) for f, size, position, start in
+                zip(p.file[a:b].tolist(), p.size[a:b].tolist(), p.position[a:b].tolist(), p.start[a:b].tolist())]
+
+    def __iter__(self):
+        return (self._digest(g) for g in range(len(self)))
+
+    def __getitem__(self, digest):
+        if self._slot is None:
+            self._slot = {self._digest(g): g for g in range(len(self))}
+        return self._references(self._slot[bytes(digest)])
+
+    def items(self):
+        return ((self._digest(g), self._references(g)) for g in range(len(self)))
+
+    def values(self):
+        return (self._references(g) for g in range(len(self)))
+
+
+@dataclass
+class RestorePlanArrays:
+    """``RestorePlan`` without a tuple per reference.  Chunk g of the u distinct chunks, in the
+    order the reference first meets them, has the digest ``digests[g]`` and the references
+    ``ref_first[g] .. ref_first[g + 1] - 1``, in the order the reference collects them: reference
+    r writes ``size[r]`` bytes from ``start[r]`` of the chunk to ``position[r]`` of ``paths[file[r]]``.
+    ``files`` maps every path to be restored to its size, as in ``RestorePlan``."""
+    digests: np.ndarray
+    ref_first: np.ndarray
+    file: np.ndarray
+    size: np.ndarray
+    position: np.ndarray
+    start: np.ndarray
+    paths: List[str]
+    files: Dict[str, int]
+
+    @property
+    def total_bytes(self) -> int:
+        return sum(self.files.values())
+
+    @property
+    def chunks_references(self) -> _ReferencesView:
+        return _ReferencesView(self)
+
+
+def _walk_host(sp, mask):
+    """The parts of the files ``mask`` chooses, each file's in counter order (stable): their file,
+    size, position, start and index."""
+    first = sp.part_first.astype(np.int64)
+    file_of = np.repeat(np.arange(first.size - 1), np.diff(first))
+    order = np.arange(file_of.size) if sp.sorted else np.lexsort((sp.counter, file_of))
+    keep = order[mask[file_of[order]]]
+    return (file_of[keep], sp.end[keep].astype(np.int64) - sp.start[keep], sp.position[keep].astype(np.int64),
+            sp.start[keep].astype(np.int64), sp.index[keep].astype(np.int64))
+
+
+def _group_host(names):
+    """The references (rows of ``names``, in walk order) grouped by name: the permutation that puts
+    every group's references together, in walk order, the groups in the order of their first
+    reference; the first reference of every group; and ``ref_first``."""
+    if not len(names):
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(1, dtype=np.int64)
+    _, head, group, counts = np.unique(names, axis=0, return_index=True, return_inverse=True, return_counts=True)
+    by_first = np.argsort(head, kind='stable')  # the distinct names in the order of their first reference
+    rank = np.empty(head.size, dtype=np.int64)
+    rank[by_first] = np.arange(head.size)
+    order = np.argsort(rank[group.reshape(-1)], kind='stable')
+    ref_first = np.concatenate([[0], np.cumsum(counts[by_first])]).astype(np.int64)
+    return order, head[by_first], ref_first
+
+
+def _plan_device(index, walks, tables, width):
+    """``_walk_host`` and ``_group_host`` on the device of ``index`` (a ``GpuChunkIndex`` of names of
+    ``width`` bytes): torch for the compaction, the gather of the digests and the two stable
+    sorts, rc_index_resolve_names_device for the groups -- a name's owner, the smallest id that
+    carries it, is its group."""
+    import torch
+    dev = torch.device('cuda', index.device)
+    cols, names = [], []
+    with torch.cuda.device(dev):
+        def up(a, dt):
+            return torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(dev)
+
+        for (sp, mask, base), table in zip(walks, tables):
+            counts = up(np.diff(sp.part_first.astype(np.int64)), np.int64)
+            file_of = torch.repeat_interleave(torch.arange(counts.numel(), device=dev), counts)
+            start, end, at = up(sp.start, np.int64), up(sp.end, np.int64), up(sp.index, np.int64)
+            position, counter = up(sp.position, np.int64), up(sp.counter, np.int64)
+            order = (torch.arange(file_of.numel(), device=dev) if sp.sorted
+                     else torch.sort((file_of << 32) | counter, stable=True).indices)
+            keep = order[up(mask, np.bool_)[file_of[order]]]
+            at = at[keep]
+            if keep.numel() and int(at.max()) >= len(table):
+                raise IndexError('list index out of range')
+            slots = np.zeros((len(table), SLOT), dtype=np.uint8)
+            slots[:, :width] = table
+            names.append(torch.from_numpy(slots).to(dev)[at])
+            cols.append(torch.stack([file_of[keep] + base, end[keep] - start[keep], position[keep], start[keep]]))
+        cols = torch.cat(cols, dim=1) if cols else torch.zeros((4, 0), dtype=torch.int64, device=dev)
+        n = cols.shape[1]
+        if not n:
+            return cols.cpu().numpy(), np.zeros((0, width), dtype=np.uint8), np.zeros(1, dtype=np.int64)
+        names = torch.cat(names).contiguous()
+        owner = torch.empty(n, dtype=torch.int64, device=dev)
+        fresh = torch.empty(n, dtype=torch.uint8, device=dev)
+        index.resolve_names(n, names.data_ptr(), owner.data_ptr(), fresh.data_ptr(),
+                            torch.cuda.current_stream(dev).cuda_stream)
+        if int(owner.min()) < 0:
+            raise RuntimeError('chunk index: a lookup exhausted its probe bound')
+        _, group = torch.unique(owner, return_inverse=True)
+        walk = torch.arange(n, device=dev)
+        head = torch.full((int(group.max()) + 1,), n, dtype=torch.int64, device=dev).scatter_reduce_(
+            0, group, walk, reduce='amin')
+        rank = torch.empty_like(head)
+        rank[torch.sort(head, stable=True).indices] = torch.arange(head.numel(), device=dev)
+        order = torch.sort(rank[group], stable=True).indices
+        head = torch.sort(head).values
+        counts = torch.bincount(rank[group], minlength=head.numel())
+        ref_first = np.concatenate([[0], np.cumsum(counts.cpu().numpy())]).astype(np.int64)
+        return cols[:, order].cpu().numpy(), names[head][:, :width].cpu().numpy(), ref_first
+
+
+def plan_restore_arrays(loaded, file_regex=None, *, index=None) -> RestorePlanArrays:
+    """``plan_restore`` over snapshots loaded with ``parts=True`` (``LoadedSnapshot`` objects whose
+    ``data`` is a ``SnapshotParts`` or None), without an object per part.  The host keeps what runs
+    over the files -- readable snapshots newest first, the first occurrence of a path wins,
+    ``file_regex.search`` -- and hands the per-part work a mask of chosen files per snapshot.
+
+    With ``index`` (a ``dedup.GpuChunkIndex`` of names of the digests' size, which takes one id per
+    reference) that work runs on its device; without one, the same steps run in numpy.  An index
+    at or beyond its snapshot's table raises ``IndexError`` before anything is returned, like the
+    reference's list lookup."""
+    pattern = re.compile(file_regex) if isinstance(file_regex, (str, bytes)) else file_regex
+    readable = [snap for snap in loaded if snap.data is not None]
+    readable.sort(key=lambda snap: snap.data.utc_timestamp, reverse=True)
+    files: Dict[str, int] = {}
+    paths: List[str] = []
+    walks, tables = [], []
+    for snap in readable:
+        sp = snap.data
+        if sp.part_first is None:
+            raise ValueError(f'{snap.path}: its parts do not fit arrays; plan_restore reads the dict')
+        table = snap.digests if snap.digests is not None else np.asarray(
+            [np.frombuffer(c, dtype=np.uint8) for c in snap.chunks], dtype=np.uint8).reshape(len(snap.chunks), -1)
+        sizes = sp.file_size.tolist()
+        mask = np.zeros(len(sizes), dtype=bool)
+        base = len(paths)  # file k of this snapshot is paths[base + k]
+        for k, entry in enumerate(sp.files):
+            path = entry['path']
+            paths.append(path)
+            if path in files or (pattern is not None and pattern.search(path) is None):
+                continue
+            mask[k] = True
+            files[path] = sizes[k]
+        walks.append((sp, mask, base))
+        tables.append(table)
+    width = tables[0].shape[1] if tables else 0
+    if index is not None:
+        cols, digests, ref_first = _plan_device(index, walks, tables, width)
+    else:
+        cols, names = [], []
+        for (sp, mask, base), table in zip(walks, tables):
+            file_of, size, position, start, at = _walk_host(sp, mask)
+            if at.size and int(at.max()) >= len(table):
+                raise IndexError('list index out of range')
+            names.append(table[at])
+            cols.append(np.stack([file_of + base, size, position, start]))
+        cols = np.concatenate(cols, axis=1) if cols else np.zeros((4, 0), dtype=np.int64)
+        names = np.concatenate(names) if names else np.zeros((0, width), dtype=np.uint8)
+        order, head, ref_first = _group_host(names)
+        cols, digests = cols[:, order], names[head]
+    return RestorePlanArrays(np.ascontiguousarray(digests), ref_first, cols[0], cols[1], cols[2], cols[3], paths, files)
 
 
 def write_file_part(path, data, offset) -> None:
@@ -418,6 +609,6 @@ class DeviceRestorer:
                 write_file_part(dest(path), contents[start:start + size], position)
 
 
-__all__ = ['plan_restore', 'RestorePlan', 'RestoreResult', 'DeviceRestorer', 'write_file_part',
-           'ChunkCorrupted', 'DecryptionError', 'ChunkEncryption', 'RC_CHUNK_OK', 'RC_CHUNK_BAD_TAG',
+__all__ = ['plan_restore', 'plan_restore_arrays', 'RestorePlan', 'RestorePlanArrays', 'RestoreResult',
+           'DeviceRestorer', 'write_file_part', 'ChunkCorrupted', 'DecryptionError', 'ChunkEncryption', 'RC_CHUNK_OK', 'RC_CHUNK_BAD_TAG',
            'RC_CHUNK_CORRUPT']

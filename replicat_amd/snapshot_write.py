@@ -43,23 +43,11 @@ from .chunker import _current_device, _ptr_array
 from .hashing import SLOT, hasher_from_config, hashlib_from_config, state_init
 from .naming import ChunkNaming, snapshot_location
 from .pipeline import ChunkEncryption, DeviceSnapshotProducer, hashing_arguments
-from .snapshots import _ENC_HEAD, _ENC_MID, _ENC_TAIL, _PLAIN_MID, _Buffers, _up
+from .snapshots import _ENC_HEAD, _ENC_MID, _ENC_TAIL, _PLAIN_MID, _Buffers, _up, serialize, type_hint
 
 _PLAIN_HEAD = b'{"chunks":'
 NONCE_PREFIX = 64   # bytes of a table's text an injected nonce rule is shown
 SMALL_PIECE = 4096  # fixed parts shorter than this are placed by one scatter
-
-
-def type_hint(obj):
-    """utils.type_hint (replicat/utils/__init__.py:166-172), the ``default`` of serialize."""
-    if isinstance(obj, (bytes, bytearray)):
-        return {'!b': str(base64.standard_b64encode(obj), 'ascii')}
-    raise TypeError
-
-
-def serialize(obj) -> bytes:
-    """Repository.serialize (repository.py:434-438)."""
-    return bytes(json.dumps(obj, separators=(',', ':'), default=type_hint), 'ascii')
 
 
 def assemble_encrypted(chunks_blob, data_blob) -> bytes:

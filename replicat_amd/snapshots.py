@@ -21,7 +21,10 @@ parse), decodes their base64 on the device, hashes ``data`` there (or, when it i
 threads: ``DeviceSnapshotProducer.HOST_DIGEST_MIN_BY_HASH``), derives the subkeys, decrypts the
 tables and decodes them into 64-byte digest slots, which go straight into a ``GpuChunkGC`` when
 one is given.  Only ``data`` -- irregular JSON -- is deserialised on the host, and only when asked
-for.
+for.  With ``parts=True`` the one array inside ``data`` that grows with the chunks, the parts of
+every file, is read on the device too (include/replicat_snapshot.h, "Reading `data`"): ``data``
+is then a ``SnapshotParts`` -- arrays, sizes, counts and positions -- and the host's json.loads
+sees only the text that is left when the parts are taken out (``accept_stripped``).
 
 The device accepts CANONICAL input only: the envelope, base64 and table text that ``serialize``
 writes.  ``json.loads`` and ``base64.standard_b64decode`` accept more (whitespace, stray
@@ -45,12 +48,13 @@ import os
 import re
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import Any, Callable, Iterable, List, Optional, Tuple
 
 import numpy as np
 
-from ._lib import (RC_CIPHER_AES_GCM, RC_CIPHER_CHACHA20_POLY1305, RC_CIPHER_NONE, RC_TABLE_BAD_TAG,
-                   RC_TABLE_NOT_CANONICAL, RC_TABLE_OK, check, lib)
+from ._lib import (RC_CIPHER_AES_GCM, RC_CIPHER_CHACHA20_POLY1305, RC_CIPHER_NONE, RC_PARTS_NOT_CANONICAL, RC_PARTS_OK,
+                   RC_TABLE_BAD_TAG, RC_TABLE_NOT_CANONICAL, RC_TABLE_OK, check, lib)
 from .chunker import _current_device, _ptr_array
 from .cipher import DecryptionError
 from .hashing import SLOT, hasher_from_config, hashlib_from_config, state_init
@@ -79,6 +83,18 @@ def type_reverse(obj):
 def deserialize(data):
     """Repository.deserialize (repository.py:440-444)."""
     return json.loads(data, object_hook=type_reverse)
+
+
+def type_hint(obj):
+    """utils.type_hint (replicat/utils/__init__.py:166-172), the ``default`` of serialize."""
+    if isinstance(obj, (bytes, bytearray)):
+        return {'!b': str(base64.standard_b64encode(obj), 'ascii')}
+    raise TypeError
+
+
+def serialize(obj) -> bytes:
+    """Repository.serialize (repository.py:434-438)."""
+    return bytes(json.dumps(obj, separators=(',', ':'), default=type_hint), 'ascii')
 
 
 def split_encrypted(contents) -> Optional[Tuple[int, int, int, int]]:
@@ -140,13 +156,184 @@ class LoadedSnapshot:
     chunks: Optional[list] = field(default=None, repr=False)  # a fallback's table as deserialised
 
     def body(self) -> dict:
-        """The reference's ``{'chunks': [bytes, ...], 'data': ...}`` (plan_restore, plan_delete)."""
+        """The reference's ``{'chunks': [bytes, ...], 'data': ...}`` (plan_restore, plan_delete).  A
+        ``data`` loaded with ``parts=True`` is turned back into the reference's dict
+        (``SnapshotParts.to_dict()``: one dict per part again); ``plan_restore_arrays`` takes the
+        loaded snapshots themselves and builds none."""
+        data = self.data.to_dict() if isinstance(self.data, SnapshotParts) else self.data
         if self.chunks is not None:
-            return {'chunks': self.chunks, 'data': self.data}
+            return {'chunks': self.chunks, 'data': data}
         if self.digests is None:
             raise ValueError(f'{self.path}: loaded without its digests (want_chunks=False)')
         flat, width = self.digests.tobytes(), self.digests.shape[1]
-        return {'chunks': [flat[i:i + width] for i in range(0, len(flat), width)], 'data': self.data}
+        return {'chunks': [flat[i:i + width] for i in range(0, len(flat), width)], 'data': data}
+
+
+LIST_OPEN = b'"chunks":['  # what serialize writes in front of a file's parts, and nowhere else
+PART_MIN_LEN = 38          # rc_snapshot_part_len_for(0, 0, 0, 0): a part's text with its separator
+
+
+def parts_room(text_len: int) -> int:
+    """rc_snapshot_parts_room: the most parts a canonical text of ``text_len`` bytes holds."""
+    return int(text_len) // PART_MIN_LEN + 1
+
+
+def positions_of(part_first, sizes, counters) -> np.ndarray:
+    """``chunk_position`` (repository.py:1795-1811) of every part, in listed order: the summed
+    sizes of the parts before it in its file when the file's parts are taken in counter order
+    (``sorted(..., key=counter)``, stable)."""
+    part_first = np.asarray(part_first, dtype=np.int64)
+    sizes = np.asarray(sizes, dtype=np.uint64)
+    file_of = np.repeat(np.arange(part_first.size - 1), np.diff(part_first))
+    order = np.lexsort((np.asarray(counters), file_of))  # stable: equal counters keep their listed order
+    before = np.concatenate([[0], np.cumsum(sizes[order], dtype=np.uint64)]).astype(np.uint64)
+    position = np.empty(sizes.size, dtype=np.uint64)
+    position[order] = before[:-1] - before[part_first[file_of]]
+    return position
+
+
+class SnapshotParts:
+    """A snapshot's ``data`` with the parts of its files as arrays instead of one dict per part.
+
+    ``files`` are the per-file dicts of the reference with ``chunks`` emptied; file k's parts
+    are ``part_first[k] .. part_first[k + 1] - 1`` of ``start``, ``end``, ``index``, ``counter``
+    (uint32, in the order the file lists them) and ``position`` (uint64: where the part's bytes go in
+    the file, ``chunk_position`` of repository.py:1795-1811).  ``file_size[k]`` and
+    ``file_chunks[k]`` are what ``list-files`` prints, ``size`` what ``list-snapshots`` prints,
+    ``sorted`` says that every file listed its parts by strictly increasing counter.  A dict the
+    device did not read (``from_dict``) that does not fit the arrays -- a part that is no dict
+    of three integers below 2^32 -- has ``part_first`` None and only ``to_dict()``."""
+
+    def __init__(self, data, part_first, start, end, index, counter, position, file_size, file_chunks, size,
+                 sorted, raw=None):
+        self._data, self._raw = data, raw
+        self.part_first, self.start, self.end, self.index, self.counter = part_first, start, end, index, counter
+        self.position, self.file_size, self.file_chunks = position, file_size, file_chunks
+        self.size, self.sorted = size, sorted
+
+    @property
+    def files(self) -> list:
+        return self._data['files']
+
+    @property
+    def utc_timestamp(self):
+        return self._data['utc_timestamp']
+
+    @property
+    def note(self):
+        return self._data.get('note')
+
+    def __eq__(self, other):
+        if isinstance(other, SnapshotParts):
+            other = other.to_dict()
+        return self.to_dict() == other
+
+    __hash__ = None
+
+    def to_dict(self):
+        """Exactly the reference's ``data``: one dict per part again."""
+        if self._raw is not None:
+            return self._raw
+        out = dict(self._data)
+        first = self.part_first.tolist()
+        cols = [a.tolist() for a in (self.start, self.end, self.index, self.counter)]
+        files = []
+        for k, entry in enumerate(self._data['files']):
+            entry = dict(entry)
+            entry['chunks'] = [{'range': [cols[0][p], cols[1][p]], 'index': cols[2][p], 'counter': cols[3][p]}
+                               for p in range(first[k], first[k + 1])]
+            files.append(entry)
+        out['files'] = files
+        return out
+
+    @classmethod
+    def from_dict(cls, data):
+        """The same object over a dict the host deserialised (a fallback); ``to_dict()`` is that dict."""
+        top = 1 << 32
+        try:
+            files = data['files']
+            counts = [len(entry['chunks']) for entry in files]
+            rows = [(p['range'][0], p['range'][1], p['index'], p['counter']) for entry in files for p in entry['chunks']]
+            fits = all(type(v) is int and 0 <= v < top for row in rows for v in row) and \
+                all(len(p['range']) == 2 and len(p) == 3 for entry in files for p in entry['chunks']) and \
+                all(row[0] <= row[1] for row in rows)
+            stripped = dict(data)
+            stripped['files'] = [{**entry, 'chunks': []} for entry in files]
+        except (KeyError, TypeError, IndexError, ValueError):
+            fits = False
+        if not fits:
+            return cls(data, None, None, None, None, None, None, None, None, None, None, raw=data)
+        cols = np.asarray(rows, dtype=np.uint32).reshape(len(rows), 4)
+        part_first = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
+        sizes = (cols[:, 1] - cols[:, 0]).astype(np.uint64)
+        before = np.concatenate([[0], np.cumsum(sizes, dtype=np.uint64)]).astype(np.uint64)
+        first = part_first.astype(np.int64)
+        file_size = before[first[1:]] - before[first[:-1]]
+        rising = np.ones(len(rows), dtype=bool)
+        rising[1:] = cols[1:, 3] > cols[:-1, 3]
+        rising[first[:-1][first[:-1] < len(rows)]] = True
+        return cls(stripped, part_first, cols[:, 0].copy(), cols[:, 1].copy(), cols[:, 2].copy(), cols[:, 3].copy(),
+                   positions_of(part_first, sizes, cols[:, 3]), file_size, np.diff(part_first).astype(np.uint64),
+                   int(sizes.sum()), bool(rising.all()), raw=data)
+
+
+def accept_stripped(stripped: bytes, run_close) -> Optional[Tuple[dict, np.ndarray]]:
+    """The host's half of reading ``data`` on the device.  ``stripped`` is the text with the parts
+    of every list taken out, ``run_close[r]`` where the ``]`` of list r stands in it.  Returns the
+    deserialised dict and the file every list belongs to, or None when the text is not one the
+    device may have read for the host:
+
+    * ``deserialize(stripped)`` -- the reference's json.loads with type_reverse -- is a dict whose
+      ``files`` is a list of dicts, each with ``chunks == []``;
+    * ``serialize`` of that dict is ``stripped`` again, so the text is exactly what serialize
+      writes (json.loads takes more: whitespace, other escapes), every quote inside a string is
+      escaped and ``"chunks":[`` occurs only where a key ``chunks`` has a list;
+    * it occurs as often as there are files: the k-th occurrence is then the list of file k;
+    * every list's ``]`` stands right behind one of the occurrences."""
+    try:
+        data = deserialize(stripped)
+        if not isinstance(data, dict) or not isinstance(data.get('files'), list):
+            return None
+        files = data['files']
+        if not all(isinstance(entry, dict) and isinstance(entry.get('chunks'), list) and not entry['chunks']
+                   for entry in files):
+            return None
+        if serialize(data) != bytes(stripped):
+            return None
+    except Exception:  # whatever json, base64 or the recursion limit raise: the reference's path decides
+        return None
+    opens = np.fromiter((m.end() for m in re.finditer(re.escape(LIST_OPEN), stripped)), dtype=np.int64)
+    if opens.size != len(files):
+        return None
+    close = np.asarray(run_close, dtype=np.int64)
+    run_file = np.searchsorted(opens, close)
+    if close.size and (run_file.max() >= opens.size or (opens[run_file] != close).any() or
+                       (np.diff(run_file) <= 0).any()):
+        return None
+    return data, run_file
+
+
+@dataclass
+class TextParts:
+    """What the device read from one text (``GpuSnapshotLoader.parse_device``).  Everything but
+    ``status`` is set only when it is RC_PARTS_OK; the arrays per part are in listed order."""
+    status: int = RC_PARTS_NOT_CANONICAL
+    stripped: Optional[bytes] = None            # the text with the parts of every list (run) taken out
+    part_first: Optional[np.ndarray] = None     # per run its first part; the number of parts behind the last
+    run_close: Optional[np.ndarray] = None      # per run where its ']' stands in the stripped text
+    run_count: Optional[np.ndarray] = None      # per run its parts
+    run_size: Optional[np.ndarray] = None       # per run the sum of end - start
+    run_sorted: Optional[np.ndarray] = None     # per run whether its counters rise strictly as listed
+    start: Optional[np.ndarray] = None
+    end: Optional[np.ndarray] = None
+    index: Optional[np.ndarray] = None
+    counter: Optional[np.ndarray] = None
+    position: Optional[np.ndarray] = None       # chunk_position of repository.py:1795-1811
+    size: int = 0                               # the sum of end - start over all parts
+    # with full=True
+    run: Optional[np.ndarray] = None            # the list of every part, counted from the text's first
+    offset: Optional[np.ndarray] = None         # of the part's text in the text
+    flags: Optional[np.ndarray] = None          # RC_PART_FIRST, RC_PART_LAST
 
 
 class _Buffers:
@@ -326,13 +513,18 @@ class GpuSnapshotLoader:
     # --------------------------------------------------------------------------- load
 
     def load(self, items, *, into=None, select: Optional[Callable[[str], bool]] = None,
-             want_chunks=True, want_data=True) -> List[LoadedSnapshot]:
+             want_chunks=True, want_data=True, parts=False) -> List[LoadedSnapshot]:
         """Load ``(path, contents)`` pairs: the location and the file bytes as downloaded or read
         from the cache.  With ``into`` (a ``GpuChunkGC``), the digests of every loaded snapshot
         for which ``select(path)`` is true (all, when ``select`` is None) are added to the
         planner as references, on the device; with ``want_chunks`` false they are never copied
         back.  ``want_data`` false skips the decryption of ``data`` of an encrypted repository.
         A ``chunks`` field whose tag does not verify raises ``DecryptionError`` naming the path.
+        With ``parts`` (and ``want_data``) the parts inside ``data`` are read on the device where
+        the text lies and ``data`` is a ``SnapshotParts``: only the text without the parts and the
+        arrays are copied back, and ``stats['data_bytes_copied_back']`` counts that text.  A
+        ``data`` the device does not accept (``accept_stripped``) is deserialised on the host as
+        before, counts in ``stats['host_fallbacks']`` and gives the same object.
         The result is in the order of ``items``."""
         if not self._h:
             raise RuntimeError('GpuSnapshotLoader is closed')
@@ -345,7 +537,7 @@ class GpuSnapshotLoader:
         def flush():
             nonlocal batch, size
             if batch:
-                run(batch, out, into, select, want_chunks, want_data)
+                run(batch, out, into, select, want_chunks, want_data, bool(parts and want_data))
             batch, size = [], 0
 
         for pos, (path, contents) in enumerate(items):
@@ -359,6 +551,10 @@ class GpuSnapshotLoader:
             batch.append((pos, path, contents, spans))
             size += len(contents)
         flush()
+        if parts and want_data:  # whatever path loaded it, callers see one type
+            for snap in out:
+                if snap.data is not None and not isinstance(snap.data, SnapshotParts):
+                    snap.data = SnapshotParts.from_dict(snap.data)
         self.stats['snapshots'] += len(items)
         return out
 
@@ -395,6 +591,195 @@ class GpuSnapshotLoader:
         self.stats['bytes_uploaded'] += total
         return d
 
+    # -------------------------------------------------------------------- parts of `data`
+
+    def read_timing_read(self) -> dict:
+        """Summed kernel milliseconds of the four stages that read ``data`` since the last read."""
+        ms = [ctypes.c_double() for _ in range(4)]
+        calls = ctypes.c_uint64()
+        check(lib().rc_snapshot_read_timing_read(self._h, *(ctypes.byref(m) for m in ms), ctypes.byref(calls)))
+        return {'find_ms': ms[0].value, 'parse_ms': ms[1].value, 'sums_ms': ms[2].value, 'strip_ms': ms[3].value,
+                'find_calls': calls.value}
+
+    def _parts_begin(self, ptrs, lens, full=False):
+        """Enqueue the four stages over the device texts ``ptrs[i]`` of ``lens[i]`` bytes on the
+        loader's stream (which the caller has made current) and the copy of what the host needs to
+        size the rest.  ``_parts_finish``, after a synchronisation, fetches the arrays."""
+        torch, L = self._torch, lib()
+        job = SimpleNamespace(n=len(lens), lens=[int(x) for x in lens], full=full)
+        n = job.n
+        cap = job.cap = sum(parts_room(ln) for ln in job.lens)
+        job.out_off, total = [], 0
+        for ln in job.lens:
+            job.out_off.append(total)
+            total += _up(ln)
+
+        def room(name, nbytes):
+            t = self._buf.get('p_' + name, max(nbytes, ALIGN))
+            setattr(job, name, t)
+            return t.data_ptr()
+
+        W = 8
+        desc, rec = room('desc', 32 * n), room('rec', 32 * cap)
+        tf, rf = room('tf', W * (n + 1)), room('rf', W * (n + 1))
+        rpf, roff, rend = room('rpf', W * (cap + 1)), room('roff', W * (cap + 1)), room('rend', W * (cap + 1))
+        status, pos = room('status', n), room('pos', W * cap)
+        rcount, rsize, rsorted = room('rcount', W * cap), room('rsize', W * cap), room('rsorted', cap)
+        tsize, slen, rclose = room('tsize', W * n), room('slen', W * n), room('rclose', W * cap)
+        scratch, out = room('scratch', W * (cap + cap // 256 + 8)), room('out', total)
+        stream = self._stream.cuda_stream
+        texts, text_lens = _ptr_array(ptrs), _ptr_array(job.lens)
+        check(L.rc_snapshot_find_parts_device(self._h, n, texts.ctypes.data, text_lens.ctypes.data, desc, rec, tf, rf,
+                                              rpf, stream))
+        check(L.rc_snapshot_parse_parts_device(self._h, n, desc, cap, tf, rf, rec, roff, rend, rpf, status, stream))
+        check(L.rc_snapshot_part_sums_device(self._h, n, cap, tf, rf, rec, rpf, None, pos, rcount, rsize, rsorted,
+                                             tsize, scratch, stream))
+        check(L.rc_snapshot_strip_parts_device(self._h, n, desc, cap, rf, roff, rend, status, out, rclose, slen,
+                                               scratch, stream))
+        # tf[n + 1] | rf[n + 1] | slen[n] | tsize[n] | status[n] | whether every run is sorted
+        job.small_at = np.cumsum([0, W * (n + 1), W * (n + 1), W * n, W * n, n]).tolist()
+        job.h_small = self._buf.get('p_h_small', job.small_at[-1] + 1, pinned=True)
+        for a, t, nbytes in zip(job.small_at, (job.tf, job.rf, job.slen, job.tsize, job.status),
+                                np.diff(job.small_at).tolist()):
+            job.h_small[a:a + nbytes].copy_(t[:nbytes], non_blocking=True)
+        a = job.small_at[-1]
+        job.h_small[a:a + 1].copy_(job.rsorted[:cap].min().reshape(1), non_blocking=True)
+        self.stats['bytes_copied_back'] += a + 1
+        return job
+
+    def _parts_resort(self, job, total):
+        """A run whose counters do not rise as listed (the reference's snapshots written by several
+        workers): the positions again, over the stable order by run and counter.  The sort is
+        torch's; a part of a text that is not canonical keeps out of the runs of the others."""
+        torch = self._torch
+        n, cap = job.n, job.cap
+        rec = job.rec[:32 * cap].view(torch.int32).view(cap, 8)[:total]
+        run = (rec[:, 0].to(torch.int64) + 1) & 0xFFFFFFFF  # 0: before any list
+        counter = rec[:, 4].to(torch.int64) & 0xFFFFFFFF
+        ends = job.tf[:8 * (n + 1)].view(torch.int64)[1:].contiguous()
+        text = torch.searchsorted(ends, torch.arange(total, device=self.dev), right=True).clamp_(max=n - 1)
+        bad = (job.status[:n][text] != RC_PARTS_OK).to(torch.int64)
+        # two stable sorts, the minor key first: no packed key, so no bound on the number of runs
+        by_counter = torch.sort(counter, stable=True).indices
+        order = by_counter[torch.sort(((run << 1) | bad)[by_counter], stable=True).indices]
+        d_order = self._buf.get('p_order', 8 * cap)
+        d_order[:8 * total].view(torch.int64).copy_(order)
+        ptr = lambda t: t.data_ptr()
+        check(lib().rc_snapshot_part_sums_device(self._h, n, cap, ptr(job.tf), ptr(job.rf), ptr(job.rec), ptr(job.rpf),
+                                                 ptr(d_order), ptr(job.pos), ptr(job.rcount), ptr(job.rsize),
+                                                 ptr(job.rsorted), ptr(job.tsize), ptr(job.scratch),
+                                                 self._stream.cuda_stream))
+        self.stats['parts_resorted'] = self.stats.get('parts_resorted', 0) + 1
+
+    def _parts_finish(self, job) -> List[TextParts]:
+        """After the synchronisation behind ``_parts_begin``: copy back the stripped texts, the
+        arrays per run and the arrays per part -- nothing else -- and cut them per text.  One
+        synchronisation (two when a run has to be sorted)."""
+        torch = self._torch
+        n, cap, W = job.n, job.cap, 8
+        small = job.h_small.numpy()
+        at = job.small_at
+        tf = small[at[0]:at[1]].view(np.uint64).astype(np.int64)
+        rf = small[at[1]:at[2]].view(np.uint64).astype(np.int64)
+        slen = small[at[2]:at[3]].view(np.uint64).astype(np.int64)
+        tsize = small[at[3]:at[4]].view(np.uint64).copy()
+        status = small[at[4]:at[5]].copy()
+        all_sorted = bool(small[at[5]])
+        total, runs = min(int(tf[n]), cap), min(int(rf[n]), cap)
+        good = [i for i in range(n) if status[i] == RC_PARTS_OK]
+        words = 8 if job.full else 4
+        with torch.cuda.stream(self._stream):
+            if not all_sorted and total:
+                self._parts_resort(job, total)
+                h_tsize = self._buf.get('p_h_tsize', W * n, pinned=True)
+                h_tsize[:W * n].copy_(job.tsize[:W * n], non_blocking=True)
+            rec = job.rec[:32 * cap].view(torch.int32).view(cap, 8)[:total]
+            cols = (rec if job.full else rec[:, 1:5]).t().contiguous()  # one row per field
+            part_bytes = 4 * words * total + W * total
+            run_bytes = W * (runs + 1) + 3 * W * runs + runs
+            text_bytes = sum(int(slen[i]) for i in good)
+            h_parts = self._buf.get('p_h_parts', max(part_bytes, ALIGN), pinned=True)
+            h_runs = self._buf.get('p_h_runs', max(_up(run_bytes) + 4 * ALIGN, ALIGN), pinned=True)
+            h_out = self._buf.get('p_h_out', max(text_bytes, ALIGN), pinned=True)
+            if total:
+                h_parts[:4 * words * total].copy_(cols.view(-1).view(torch.uint8), non_blocking=True)
+                h_parts[4 * words * total:part_bytes].copy_(job.pos[:W * total], non_blocking=True)
+            run_at = np.cumsum([0, _up(W * (runs + 1)), _up(W * runs), _up(W * runs), _up(W * runs)]).tolist()
+            for a, t, nbytes in zip(run_at, (job.rpf, job.rcount, job.rsize, job.rclose, job.rsorted),
+                                    (W * (runs + 1), W * runs, W * runs, W * runs, runs)):
+                if nbytes:
+                    h_runs[a:a + nbytes].copy_(t[:nbytes], non_blocking=True)
+            text_at, o = {}, 0
+            for i in good:
+                text_at[i] = o
+                if slen[i]:
+                    h_out[o:o + int(slen[i])].copy_(job.out[job.out_off[i]:job.out_off[i] + int(slen[i])],
+                                                    non_blocking=True)
+                o += int(slen[i])
+            self._stream.synchronize()
+        self.stats['bytes_copied_back'] += part_bytes + run_bytes + text_bytes
+        self.stats['data_bytes_copied_back'] += text_bytes
+        if not all_sorted and total:
+            tsize = h_tsize.numpy()[:W * n].view(np.uint64).copy()
+        parts_np, runs_np, out_np = h_parts.numpy(), h_runs.numpy(), h_out.numpy()
+        cols = parts_np[:4 * words * total].view(np.uint32).reshape(words, total)
+        position = parts_np[4 * words * total:part_bytes].view(np.uint64)
+        rpf = runs_np[run_at[0]:run_at[0] + W * (runs + 1)].view(np.uint64).astype(np.int64)
+        rcount, rsize, rclose = (runs_np[a:a + W * runs].view(np.uint64) for a in run_at[1:4])
+        rsorted = runs_np[run_at[4]:run_at[4] + runs]
+        result = []
+        for i in range(n):
+            tp = TextParts()
+            tp.status = int(status[i])
+            result.append(tp)
+            if tp.status != RC_PARTS_OK:
+                continue
+            a, b, ra, rb = int(tf[i]), int(tf[i + 1]), int(rf[i]), int(rf[i + 1])
+            tp.stripped = out_np[text_at[i]:text_at[i] + int(slen[i])].tobytes()
+            tp.part_first = np.concatenate([rpf[ra:rb], [b]]).astype(np.uint64) - np.uint64(a)
+            tp.run_close, tp.run_count, tp.run_size = rclose[ra:rb].copy(), rcount[ra:rb].copy(), rsize[ra:rb].copy()
+            tp.run_sorted = rsorted[ra:rb].astype(bool)
+            first = 1 if job.full else 0
+            tp.start, tp.end, tp.index, tp.counter = (cols[first + c, a:b].copy() for c in range(4))
+            tp.position = position[a:b].copy()
+            tp.size = int(tsize[i])
+            if job.full:
+                tp.run = (cols[0, a:b].astype(np.int64) - ra).astype(np.int64)
+                tp.offset = cols[5, a:b].astype(np.uint64) | (cols[6, a:b].astype(np.uint64) << np.uint64(32))
+                tp.flags = cols[7, a:b].copy()
+        return result
+
+    def parse_device(self, ptrs, lens, full=True) -> List[TextParts]:
+        """Read the parts of n texts that lie in device memory (``ptrs[i]``, ``lens[i]`` bytes, any
+        alignment), in one call: what ``load(parts=True)`` runs on every ``data``, for tests and
+        probes."""
+        if not self._h:
+            raise RuntimeError('GpuSnapshotLoader is closed')
+        if not len(lens):
+            return []
+        with self._torch.cuda.stream(self._stream):
+            job = self._parts_begin(ptrs, lens, full)
+            self._stream.synchronize()
+        return self._parts_finish(job)
+
+    @staticmethod
+    def parts_of(tp: TextParts) -> Optional[SnapshotParts]:
+        """The acceptance rule: ``SnapshotParts`` from what the device read, or None when the
+        snapshot has to take the host's ``deserialize``."""
+        if tp.status != RC_PARTS_OK:
+            return None
+        accepted = accept_stripped(tp.stripped, tp.run_close)
+        if accepted is None:
+            return None
+        data, run_file = accepted
+        m = len(data['files'])
+        chunks, size = np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=np.uint64)
+        chunks[run_file] = tp.run_count
+        size[run_file] = tp.run_size
+        part_first = np.concatenate([[0], np.cumsum(chunks)]).astype(np.uint64)
+        return SnapshotParts(data, part_first, tp.start, tp.end, tp.index, tp.counter, tp.position, size, chunks,
+                             tp.size, bool(tp.run_sorted.all()))
+
     def _finish_tables(self, batch, k_of, counts, firsts, status, d_slots, slots_np, plain_of, out, into,
                        select, want_chunks, data_of):
         """The host half after a batch's statuses are known: ``k_of`` maps a batch position to
@@ -427,11 +812,21 @@ class GpuSnapshotLoader:
             runs.sort()
             self._reference_device(runs, d_slots, into)
 
-    def _run_plain(self, batch, out, into, select, want_chunks, want_data):
+    def _data_on_host(self, text) -> 'SnapshotParts':
+        """A ``data`` the device did not accept, the reference's way (raises what it raises)."""
+        data = SnapshotParts.from_dict(deserialize(text))
+        self.stats['host_fallbacks'] += 1
+        return data
+
+    def _run_plain(self, batch, out, into, select, want_chunks, want_data, parts=False):
         torch, L = self._torch, self.digest_size
-        # D first: a body whose D is not one JSON value is not of the expected shape
+        # D first: a body whose D is not one JSON value is not of the expected shape (with parts
+        # the deserialize of the stripped text says so, after the device has read D)
         datas, keep = {}, []
         for b, (pos, path, contents, (t0, t1, d0, d1)) in enumerate(batch):
+            if parts:
+                keep.append(b)
+                continue
             try:
                 datas[b] = deserialize(contents[d0:d1])
                 keep.append(b)
@@ -450,6 +845,13 @@ class GpuSnapshotLoader:
             lens.append(t1 - t0)
             pieces.append((total, memoryview(contents)[t0:t1]))
             total += _up(t1 - t0)
+        d_offs = []
+        if parts:
+            for b in keep:
+                _, _, contents, (_, _, d0, d1) = batch[b]
+                d_offs.append(total)
+                pieces.append((total, memoryview(contents)[d0:d1]))
+                total += _up(d1 - d0)
         counts = np.zeros(n, dtype=np.uint64)
         want = [self.table_count(ln) or 0 for ln in lens]
         slots = sum(want)
@@ -463,6 +865,10 @@ class GpuSnapshotLoader:
             check(lib().rc_snapshot_tables_device(self._h, n, blobs.ctypes.data, blob_lens.ctypes.data, None, None,
                                                   counts.ctypes.data, d_slots.data_ptr(), d_status.data_ptr(),
                                                   self._stream.cuda_stream))
+            job = None
+            if parts:
+                job = self._parts_begin([d_up.data_ptr() + o for o in d_offs],
+                                        [batch[b][3][3] - batch[b][3][2] for b in keep])
             h_status[:n].copy_(d_status[:n], non_blocking=True)
             slots_np = None
             if want_chunks and slots:
@@ -475,6 +881,18 @@ class GpuSnapshotLoader:
         if slots_np is None:
             slots_np = np.empty((0, SLOT), dtype=np.uint8)
         firsts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.uint64)
+        if job is not None:
+            for k, tp in enumerate(self._parts_finish(job)):
+                b = keep[k]
+                pos, path, contents, (_, _, d0, d1) = batch[b]
+                datas[b] = self.parts_of(tp)
+                if datas[b] is None:
+                    try:
+                        datas[b] = self._data_on_host(contents[d0:d1])
+                    except ValueError:
+                        out[pos] = self._fallback(path, contents, want_chunks, want_data)
+                        self._reference_host(out[pos], into, select)
+                        k_of[b] = None
 
         def plain_of(k):  # the text is on the host already
             _, _, contents, (t0, t1, _, _) = batch[keep[k]]
@@ -483,7 +901,7 @@ class GpuSnapshotLoader:
         self._finish_tables(batch, k_of, counts, firsts, h_status.numpy()[:n], d_slots, slots_np, plain_of, out,
                             into, select, want_chunks, lambda k: datas[keep[k]])
 
-    def _run_encrypted(self, batch, out, into, select, want_chunks, want_data):
+    def _run_encrypted(self, batch, out, into, select, want_chunks, want_data, parts=False):
         torch, L, over = self._torch, self.digest_size, self.overhead
         decrypt_data = bool(want_data and self.userkey is not None)
         dev_items, host_items = [], []  # (batch position, decoded X length, decoded Y length[, decoded Y])
@@ -584,7 +1002,7 @@ class GpuSnapshotLoader:
                                                   d_dd.data_ptr(), plains.ctypes.data, counts.ctypes.data,
                                                   d_slots.data_ptr(), flags_ptr, stream))
             # 4. data under the user key
-            h_data = None
+            h_data = job = None
             if decrypt_data:
                 d_key = self._buf.get('d_key', SLOT)
                 h_key = self._buf.get('h_key', SLOT, pinned=True)
@@ -601,7 +1019,9 @@ class GpuSnapshotLoader:
                         ins.append(up_ptr + y_raw[k])
                 self.cipher.decrypt_device(ins, [it[2] for it in order], [d_key.data_ptr()] * n,
                                            [d_data.data_ptr() + o for o in q_off], flags_ptr + 2 * n + m, stream)
-                if q:
+                if parts:  # read where it lies; a text whose tag failed is read too, and not used
+                    job = self._parts_begin([d_data.data_ptr() + o for o in q_off], data_lens)
+                elif q:
                     h_data = self._buf.get('h_data', q, pinned=True)
                     h_data[:q].copy_(d_data[:q], non_blocking=True)
                     self.stats['bytes_copied_back'] += q
@@ -621,6 +1041,7 @@ class GpuSnapshotLoader:
         status, ok_x, ok_y = flags[:n], flags[n:2 * n], flags[2 * n:2 * n + m]
         ok_data = flags[2 * n + m:3 * n + m]
         firsts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.uint64)
+        read = self._parts_finish(job) if job is not None else None
         # a field the bulk decoder refused: the whole reference path for that snapshot
         for k, (b, xlen, ylen, ydec) in enumerate(order):
             if not ok_x[k] or (k < m and not ok_y[k]):
@@ -639,11 +1060,21 @@ class GpuSnapshotLoader:
             if not decrypt_data or not ok_data[k]:
                 return None
             o = q_off[k]
+            if read is not None:
+                data = self.parts_of(read[k])
+                if data is None:  # not what the device reads: the plaintext comes back after all
+                    text = d_data[o:o + data_lens[k]].cpu().numpy().tobytes()
+                    self.stats['bytes_copied_back'] += data_lens[k]
+                    self.stats['data_bytes_copied_back'] += data_lens[k]
+                    data = self._data_on_host(text)
+                return data
             return deserialize(h_data.numpy()[o:o + data_lens[k]].tobytes() if h_data is not None else b'')
 
         self._finish_tables(batch, k_of, counts, firsts, status, d_slots, slots_np, plain_of, out, into, select,
                             want_chunks, data_of)
 
 
-__all__ = ['GpuSnapshotLoader', 'LoadedSnapshot', 'split_encrypted', 'split_plain', 'deserialize', 'type_reverse',
+__all__ = ['GpuSnapshotLoader', 'LoadedSnapshot', 'SnapshotParts', 'TextParts', 'accept_stripped', 'positions_of',
+           'parts_room', 'serialize', 'type_hint', 'RC_PARTS_OK', 'RC_PARTS_NOT_CANONICAL',
+           'split_encrypted', 'split_plain', 'deserialize', 'type_reverse',
            'DecryptionError', 'ChunkEncryption', 'RC_TABLE_OK', 'RC_TABLE_BAD_TAG', 'RC_TABLE_NOT_CANONICAL']
