@@ -30,7 +30,8 @@ HEADERS = [os.path.join(CSRC, n) for n in ('gclmul.h', 'digest_kernels.h', 'capi
                                              'knobs.h', 'diag.h', 'cipher_host.h', 'chacha_kernels.h',
                                              'poly1305_limbs.h', 'sha_kernels.h', 'sha_walk.h',
                                              'restore_kernels.h', 'index_kernels.h', 'index_lookup.h',
-                                             'blake2b_lane.h', 'gc_kernels.h', 'snapshot_kernels.h')] + [
+                                             'blake2b_lane.h', 'gc_kernels.h', 'snapshot_kernels.h',
+                                             'snapshot_device.h')] + [
     os.path.join(ROOT, 'include', n) for n in ('replicat_chunker.h', 'replicat_digest.h', 'replicat_cipher.h',
                                                'replicat_restore.h', 'replicat_index.h', 'replicat_gc.h',
                                                'replicat_snapshot.h')]

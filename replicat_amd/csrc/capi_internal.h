@@ -1,8 +1,9 @@
 // capi_internal.h -- the handle core every family's host file shares (capi.cpp: chunker,
 // capi_digest.cpp: hashers, cipher_host.cpp and its two ciphers, capi_restore.cpp, capi_index.cpp,
-// capi_gc.cpp) and the launchers in the .hip files report through: the error slot and the launch
-// status, the live-handle registry, the device check and guard, the growable buffers, the
-// two-slot staging ring, the event-pair timer and the shared half of *_destroy and *_timing_*.
+// capi_gc.cpp, capi_snapshot.cpp) and the launchers in the .hip files report through: the error
+// slot and the launch status, the live-handle registry, the device check and guard, the growable
+// buffers, the two-slot staging ring, the event-pair timer and the shared half of *_destroy and
+// *_timing_*.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -23,6 +23,19 @@
 static_assert(RC_TABLE_OK == RC_CHUNK_OK && RC_TABLE_BAD_TAG == RC_CHUNK_BAD_TAG,
               "the verdict kernel writes the first two table statuses");
 
+namespace {
+
+// The event pairs of a handle, one per stage (the four rc_snapshot_*timing_read).
+enum Timer {
+    kCrypt, kDecode, kB64,         // loading (snapshot.hip)
+    kEncode, kB64Encode, kSeal,    // writing (snapshot_write.hip)
+    kParts, kScan, kData,          // writing `data` (snapshot_data.hip)
+    kFind, kParse, kSums, kStrip,  // reading `data` (snapshot_parse.hip)
+    kTimers
+};
+
+}  // namespace
+
 struct rc_snapshot {
     rc_cipher::CipherCore *cipher = nullptr;  // null: RC_CIPHER_NONE
     int device = 0;
@@ -37,14 +50,8 @@ struct rc_snapshot {
     rc::SlotRing<Staging> ring;
     // blocking host path
     rc::DevBuf d_in, d_out, d_meta, d_slots;  // blobs | plaintexts | data digests[64 n] status[n] | digests
-    rc::PairTimer t_crypt, t_decode, t_b64;
-    // writing (snapshot_write.hip)
-    rc::DevBuf d_nonces;  // blocking host path: the nonces of one call
-    rc::PairTimer t_encode, t_b64_encode, t_seal;
-    // writing `data` (snapshot_data.hip)
-    rc::PairTimer t_parts, t_scan, t_data;
-    // reading `data` (snapshot_parse.hip)
-    rc::PairTimer t_find, t_parse, t_sums, t_strip;
+    rc::DevBuf d_nonces;                      // of one call that writes
+    std::array<rc::PairTimer, kTimers> timers;
 };
 
 namespace {
@@ -68,62 +75,95 @@ void list_blocks(uint64_t n, uint64_t per, Units units, std::vector<SnapBlock> &
     }
 }
 
+// One work list of a call: `bytes` at p.
+struct Span {
+    const void *p;
+    size_t bytes;
+    template <class T>
+    Span(const std::vector<T> &v) : p(v.data()), bytes(v.size() * sizeof(T)) {}
+};
+
+// The work lists of one call on the device, in the slot that holds them: list k starts at d + off[k].
+struct Staged {
+    rc::SlotRing<rc_snapshot::Staging>::Slot *w = nullptr;
+    uint8_t *d = nullptr;
+    size_t off[4] = {};
+    template <class T>
+    const T *list(int k) const {
+        return reinterpret_cast<const T *>(d + off[k]);
+    }
+};
+
+// Takes the ring's next slot, lays the lists of one call (at most four, in the order the kernels
+// read them) back to back at 16-byte offsets in its pinned staging -- an empty list takes no room
+// -- and enqueues their one upload.  The caller holds s->mu and has the device current, sizes
+// d_scratch itself and ends with s->ring.finish(*g.w, st).
+int stage_lists(rc_snapshot *s, std::initializer_list<Span> lists, hipStream_t st, Staged &g) {
+    if (int rc = s->ring.acquire(g.w)) return rc;
+    size_t total = 0, k = 0;
+    for (const Span &l : lists) total = (g.off[k++] = up16(total)) + l.bytes;
+    if (int rc = g.w->h_stage.ensure(total)) return rc;
+    if (int rc = g.w->d_stage.ensure(total)) return rc;
+    uint8_t *h = static_cast<uint8_t *>(g.w->h_stage.p);
+    g.d = static_cast<uint8_t *>(g.w->d_stage.p);
+    for (k = 0; k < lists.size(); ++k)
+        if (const Span &l = lists.begin()[k]; l.bytes) std::memcpy(h + g.off[k], l.p, l.bytes);
+    RC_HIP_TRY(hipMemcpyAsync(g.d, h, total, hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+// derive_shared_subkey for n snapshots: hash_digest(body['data']) is the message, key slot i the
+// output.  Empty without a cipher.
+std::vector<B2UItem> subkey_items(const rc_snapshot *s, uint64_t n, const uint8_t *d_data_digests) {
+    std::vector<B2UItem> items(s->cipher ? n : 0);
+    const uint64_t state = reinterpret_cast<uint64_t>(s->d_kdf.p);
+    for (uint64_t i = 0; i < items.size(); ++i)
+        items[i] = B2UItem{reinterpret_cast<uint64_t>(d_data_digests + kB2Slot * i), s->digest_bytes, i, state, 1u, 0u};
+    return items;
+}
+
+std::vector<const uint8_t *> key_pointers(const uint8_t *d_keys, uint64_t n) {
+    std::vector<const uint8_t *> keys(n);
+    for (uint64_t i = 0; i < n; ++i) keys[i] = d_keys + kB2Slot * i;
+    return keys;
+}
+
 // the caller holds s->mu and has the device current
 int tables_locked(rc_snapshot *s, uint64_t n, const uint8_t *const *d_blobs, const uint64_t *blob_lens,
                   const uint8_t *d_data_digests, uint8_t *const *d_plain, uint64_t *counts,
                   uint8_t *d_digests, uint8_t *d_status, hipStream_t st) {
     const bool enc = s->cipher != nullptr;
-    std::vector<uint64_t> plain_lens(n);
     std::vector<SnapTable> tables(n);
+    std::vector<RestorePlain> plains(enc ? n : 0);
     uint64_t first = 0;
     for (uint64_t i = 0; i < n; ++i) {
-        plain_lens[i] = blob_lens[i] > s->overhead ? blob_lens[i] - s->overhead : 0;
-        const uint64_t c = table_count(s->stride, plain_lens[i]);
+        const uint64_t plain_len = blob_lens[i] > s->overhead ? blob_lens[i] - s->overhead : 0;
+        const uint64_t c = table_count(s->stride, plain_len);
         counts[i] = c == kSnapReject ? 0 : c;
-        tables[i] = SnapTable{reinterpret_cast<uint64_t>(enc ? d_plain[i] : d_blobs[i]), plain_lens[i], c, first};
+        tables[i] = SnapTable{reinterpret_cast<uint64_t>(enc ? d_plain[i] : d_blobs[i]), plain_len, c, first};
+        if (enc) plains[i] = RestorePlain{reinterpret_cast<uint64_t>(d_plain[i]), plain_len};
         first += counts[i];
     }
     std::vector<SnapBlock> blocks;
     list_blocks(n, kSnapThreads, [&](uint64_t i) { return tables[i].count; }, blocks);
-    rc::SlotRing<rc_snapshot::Staging>::Slot *w = nullptr;
-    if (int rc = s->ring.acquire(w)) return rc;
+    const std::vector<B2UItem> items = subkey_items(s, n, d_data_digests);
     // B2UItem[n] | RestorePlain[n] | SnapTable[n] | SnapBlock[]
-    const size_t plain_off = enc ? up16(n * sizeof(B2UItem)) : 0;
-    const size_t table_off = enc ? plain_off + up16(n * sizeof(RestorePlain)) : 0;
-    const size_t block_off = table_off + up16(n * sizeof(SnapTable));
-    const size_t stage = block_off + blocks.size() * sizeof(SnapBlock);
-    if (int rc = w->h_stage.ensure(stage)) return rc;
-    if (int rc = w->d_stage.ensure(stage)) return rc;
-    if (int rc = w->d_scratch.ensure(n * (kB2Slot + 1))) return rc;
-    uint8_t *h = static_cast<uint8_t *>(w->h_stage.p);
-    uint8_t *d = static_cast<uint8_t *>(w->d_stage.p);
-    uint8_t *d_keys = static_cast<uint8_t *>(w->d_scratch.p);
+    Staged g;
+    if (int rc = stage_lists(s, {items, plains, tables, blocks}, st, g)) return rc;
+    if (int rc = g.w->d_scratch.ensure(n * (kB2Slot + 1))) return rc;
+    uint8_t *d_keys = static_cast<uint8_t *>(g.w->d_scratch.p);
     uint8_t *d_ok = d_keys + n * kB2Slot;
-    if (enc) {
-        B2UItem *it = reinterpret_cast<B2UItem *>(h);
-        RestorePlain *pl = reinterpret_cast<RestorePlain *>(h + plain_off);
-        const uint64_t state = reinterpret_cast<uint64_t>(s->d_kdf.p);
-        for (uint64_t i = 0; i < n; ++i) {
-            // derive_shared_subkey: hash_digest(body['data']) is the message, key slot i the output
-            it[i] = B2UItem{reinterpret_cast<uint64_t>(d_data_digests + kB2Slot * i), s->digest_bytes, i, state, 1u, 0u};
-            pl[i] = RestorePlain{reinterpret_cast<uint64_t>(d_plain[i]), plain_lens[i]};
-        }
-    }
-    std::memcpy(h + table_off, tables.data(), n * sizeof(SnapTable));
-    std::memcpy(h + block_off, blocks.data(), blocks.size() * sizeof(SnapBlock));
-    RC_HIP_TRY(hipMemcpyAsync(d, h, stage, hipMemcpyHostToDevice, st));
     if (enc) {
         RestoreVerdictArgs a{};
         a.ok = d_ok;
         a.computed = a.expected = d_keys;  // equal: the verdict is the tag's alone
-        a.plain = reinterpret_cast<const RestorePlain *>(d + plain_off);
+        a.plain = g.list<RestorePlain>(1);
         a.status = d_status;
         a.n = n;
         a.digest_size = 1;
-        if (int rc = rc::timed(s->t_crypt, st, [&] {
-                if (int rc = rc_b2_launch_update(reinterpret_cast<const B2UItem *>(d), n, d_keys, st)) return rc;
-                std::vector<const uint8_t *> keys(n);
-                for (uint64_t i = 0; i < n; ++i) keys[i] = d_keys + kB2Slot * i;
+        if (int rc = rc::timed(s->timers[kCrypt], st, [&] {
+                if (int rc = rc_b2_launch_update(g.list<B2UItem>(0), n, d_keys, st)) return rc;
+                const std::vector<const uint8_t *> keys = key_pointers(d_keys, n);
                 if (int rc = rc_cipher::decrypt_device(s->cipher, n, d_blobs, blob_lens, keys.data(), d_plain, d_ok, st))
                     return rc;
                 return rc_restore_launch_verdict(a, st);
@@ -132,32 +172,36 @@ int tables_locked(rc_snapshot *s, uint64_t n, const uint8_t *const *d_blobs, con
     } else {
         RC_HIP_TRY(hipMemsetAsync(d_status, RC_TABLE_OK, n, st));
     }
-    if (int rc = rc::timed(s->t_decode, st, [&] {
-            return rc_snap_launch_tables(reinterpret_cast<const SnapTable *>(d + table_off),
-                                         reinterpret_cast<const SnapBlock *>(d + block_off), blocks.size(),
-                                         s->digest_bytes, d_digests, d_status, st);
+    if (int rc = rc::timed(s->timers[kDecode], st, [&] {
+            return rc_snap_launch_tables(g.list<SnapTable>(2), g.list<SnapBlock>(3), blocks.size(), s->digest_bytes,
+                                         d_digests, d_status, st);
         }))
         return rc;
-    return s->ring.finish(*w, st);
+    return s->ring.finish(*g.w, st);
 }
 
-int check_lists(const rc_snapshot *s, uint64_t n, const uint8_t *const *blobs, const uint64_t *lens,
+// What both table entry points check before a device is touched; slots = the digests of the call.
+// The blocking form (`device` false) owns the plaintexts, so it has no plain array, and its
+// digests are host memory of any alignment.
+int check_lists(const rc_snapshot *s, bool device, uint64_t n, const uint8_t *const *blobs, const uint64_t *lens,
                 const void *data_digests, uint8_t *const *plain, const void *counts, const void *digests,
-                const void *status) {
-    if (!blobs || !lens || !counts || !status || (s->cipher && (!plain || !data_digests)))
+                const void *status, uint64_t &slots) {
+    const bool enc = s->cipher != nullptr, plains = enc && device;
+    if (!blobs || !lens || !counts || !status || (plains && !plain) || (enc && !data_digests))
         return rc_fail(RC_ERR_ARGUMENT, "null arrays");
     if (n > 0xFFFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "more than 2^32 tables in one call");
-    uint64_t total = 0;
+    slots = 0;
     for (uint64_t i = 0; i < n; ++i) {
-        if ((lens[i] && !blobs[i]) || (s->cipher && lens[i] > s->overhead && !plain[i]))
+        if ((lens[i] && !blobs[i]) || (plains && lens[i] > s->overhead && !plain[i]))
             return rc_fail(RC_ERR_ARGUMENT, "table %llu: null pointer", (unsigned long long)i);
-        if (s->cipher && lens[i] > s->overhead)
+        if (enc && lens[i] > s->overhead)
             if (int rc = rc_cipher::check_len(s->cipher->desc, i, lens[i] - s->overhead)) return rc;
         const uint64_t c = table_count(s->stride, lens[i] > s->overhead ? lens[i] - s->overhead : 0);
-        total += c == kSnapReject ? 0 : c;
+        slots += c == kSnapReject ? 0 : c;
     }
-    if (total && !digests) return rc_fail(RC_ERR_ARGUMENT, "null digests");
-    if (reinterpret_cast<uintptr_t>(digests) & 15) return rc_fail(RC_ERR_ALIGN, "d_digests is not 16-byte aligned");
+    if (slots && !digests) return rc_fail(RC_ERR_ARGUMENT, "null digests");
+    if (device && (reinterpret_cast<uintptr_t>(digests) & 15))
+        return rc_fail(RC_ERR_ALIGN, "d_digests is not 16-byte aligned");
     return 0;
 }
 
@@ -195,51 +239,67 @@ int seal_locked(rc_snapshot *s, uint64_t n, const uint8_t *d_digests, const uint
                 const uint64_t *counts, const uint64_t *lens, const uint8_t *d_data_digests,
                 const uint8_t *d_nonces, uint8_t *const *d_text, uint8_t *const *d_blobs, hipStream_t st) {
     const bool enc = s->cipher != nullptr;
+    std::vector<SnapTable> tables(n);
+    for (uint64_t i = 0; i < n; ++i)
+        tables[i] = SnapTable{reinterpret_cast<uint64_t>(d_text[i]), lens[i], counts[i], firsts[i]};
     std::vector<SnapBlock> blocks;
     list_blocks(n, kSnapThreads, [&](uint64_t i) { return counts[i]; }, blocks);
-    rc::SlotRing<rc_snapshot::Staging>::Slot *w = nullptr;
-    if (int rc = s->ring.acquire(w)) return rc;
+    const std::vector<B2UItem> items = subkey_items(s, n, d_data_digests);
     // B2UItem[n] | SnapTable[n] | SnapBlock[]
-    const size_t table_off = enc ? up16(n * sizeof(B2UItem)) : 0;
-    const size_t block_off = table_off + up16(n * sizeof(SnapTable));
-    const size_t stage = block_off + blocks.size() * sizeof(SnapBlock);
-    if (int rc = w->h_stage.ensure(stage)) return rc;
-    if (int rc = w->d_stage.ensure(stage)) return rc;
+    Staged g;
+    if (int rc = stage_lists(s, {items, tables, blocks}, st, g)) return rc;
     if (enc)
-        if (int rc = w->d_scratch.ensure(n * kB2Slot)) return rc;
-    uint8_t *h = static_cast<uint8_t *>(w->h_stage.p);
-    uint8_t *d = static_cast<uint8_t *>(w->d_stage.p);
-    uint8_t *d_keys = static_cast<uint8_t *>(w->d_scratch.p);
-    SnapTable *tables = reinterpret_cast<SnapTable *>(h + table_off);
-    for (uint64_t i = 0; i < n; ++i) {
-        tables[i] = SnapTable{reinterpret_cast<uint64_t>(d_text[i]), lens[i], counts[i], firsts[i]};
-        if (enc) {
-            const uint64_t state = reinterpret_cast<uint64_t>(s->d_kdf.p);
-            reinterpret_cast<B2UItem *>(h)[i] =
-                B2UItem{reinterpret_cast<uint64_t>(d_data_digests + kB2Slot * i), s->digest_bytes, i, state, 1u, 0u};
-        }
-    }
-    std::memcpy(h + block_off, blocks.data(), blocks.size() * sizeof(SnapBlock));
-    RC_HIP_TRY(hipMemcpyAsync(d, h, stage, hipMemcpyHostToDevice, st));
-    if (int rc = rc::timed(s->t_encode, st, [&] {
-            return rc_snap_launch_encode_tables(reinterpret_cast<const SnapTable *>(d + table_off),
-                                                reinterpret_cast<const SnapBlock *>(d + block_off), blocks.size(),
+        if (int rc = g.w->d_scratch.ensure(n * kB2Slot)) return rc;
+    uint8_t *d_keys = static_cast<uint8_t *>(g.w->d_scratch.p);
+    if (int rc = rc::timed(s->timers[kEncode], st, [&] {
+            return rc_snap_launch_encode_tables(g.list<SnapTable>(1), g.list<SnapBlock>(2), blocks.size(),
                                                 s->digest_bytes, d_digests, st);
         }))
         return rc;
     if (enc) {
-        if (int rc = rc::timed(s->t_seal, st, [&] {
-                if (int rc = rc_b2_launch_update(reinterpret_cast<const B2UItem *>(d), n, d_keys, st)) return rc;
-                std::vector<const uint8_t *> keys(n), nonces(n);
-                for (uint64_t i = 0; i < n; ++i) {
-                    keys[i] = d_keys + kB2Slot * i;
-                    nonces[i] = d_nonces + uint64_t(s->cipher->desc.nonce_bytes) * i;
-                }
+        if (int rc = rc::timed(s->timers[kSeal], st, [&] {
+                if (int rc = rc_b2_launch_update(g.list<B2UItem>(0), n, d_keys, st)) return rc;
+                const std::vector<const uint8_t *> keys = key_pointers(d_keys, n);
+                std::vector<const uint8_t *> nonces(n);
+                for (uint64_t i = 0; i < n; ++i) nonces[i] = d_nonces + uint64_t(s->cipher->desc.nonce_bytes) * i;
                 return rc_cipher::encrypt_device(s->cipher, n, d_text, lens, keys.data(), nonces.data(), d_blobs, st);
             }))
             return rc;
     }
-    return s->ring.finish(*w, st);
+    return s->ring.finish(*g.w, st);
+}
+
+// The bulk base64 stage, either way: the texts at `per` units a workgroup through `launch` inside
+// timer t; d_ok (decoding only) is all ones beforehand.  The caller holds s->mu and has the device
+// current.
+template <class Launch>
+int bulk_locked(rc_snapshot *s, const std::vector<SnapText> &texts, uint64_t per, Launch launch, Timer t, uint8_t *d_ok,
+                hipStream_t st) {
+    std::vector<SnapBlock> blocks;
+    list_blocks(texts.size(), per, [&](uint64_t i) { return texts[i].len; }, blocks);
+    // SnapText[n] | SnapBlock[]
+    Staged g;
+    if (int rc = stage_lists(s, {texts, blocks}, st, g)) return rc;
+    if (d_ok) RC_HIP_TRY(hipMemsetAsync(d_ok, 1, texts.size(), st));
+    if (int rc = rc::timed(s->timers[t], st,
+                           [&] { return launch(g.list<SnapText>(0), g.list<SnapBlock>(1), blocks.size(), st); }))
+        return rc;
+    return s->ring.finish(*g.w, st);
+}
+
+// Behind the four *timing_read: the timers in the order given.
+struct TimerOut {
+    Timer t;
+    double *ms;
+    uint64_t *calls;
+};
+int read_timers(rc_snapshot *s, std::initializer_list<TimerOut> outs) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    for (const TimerOut &o : outs)
+        if (int rc = s->timers[o.t].read(o.ms, o.calls)) return rc;
+    return RC_OK;
 }
 
 }  // namespace
@@ -304,10 +364,7 @@ void rc_snapshot_destroy(rc_snapshot *s) {
             w.d_scratch.release();
         });
         for (rc::DevBuf *b : {&s->d_kdf, &s->d_in, &s->d_out, &s->d_meta, &s->d_slots, &s->d_nonces}) b->release();
-        for (rc::PairTimer *t : {&s->t_crypt, &s->t_decode, &s->t_b64, &s->t_encode, &s->t_b64_encode, &s->t_seal,
-                                 &s->t_parts, &s->t_scan, &s->t_data, &s->t_find, &s->t_parse, &s->t_sums,
-                                 &s->t_strip})
-            t->release();
+        for (rc::PairTimer &t : s->timers) t.release();
     });
     delete s;
 }
@@ -330,7 +387,8 @@ int rc_snapshot_tables_device(rc_snapshot *s, uint64_t n, const uint8_t *const *
                               uint8_t *d_status, void *hip_stream) {
     if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
     if (n == 0) return RC_OK;
-    if (int rc = check_lists(s, n, d_blobs, blob_lens, d_data_digests, d_plain, counts, d_digests, d_status))
+    uint64_t slots;
+    if (int rc = check_lists(s, true, n, d_blobs, blob_lens, d_data_digests, d_plain, counts, d_digests, d_status, slots))
         return rc;
     std::lock_guard<std::mutex> lock(s->mu);
     rc::DeviceGuard guard(s->device);
@@ -343,17 +401,8 @@ int rc_snapshot_tables_host(rc_snapshot *s, uint64_t n, const uint8_t *const *bl
     if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
     if (n == 0) return RC_OK;
     const bool enc = s->cipher != nullptr;
-    if (!blobs || !lens || !counts || !status || (enc && !data_digests)) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
-    if (n > 0xFFFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "more than 2^32 tables in one call");
-    uint64_t slots = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        if (lens[i] && !blobs[i]) return rc_fail(RC_ERR_ARGUMENT, "table %llu: null pointer", (unsigned long long)i);
-        if (enc && lens[i] > s->overhead)
-            if (int rc = rc_cipher::check_len(s->cipher->desc, i, lens[i] - s->overhead)) return rc;
-        const uint64_t c = table_count(s->stride, lens[i] > s->overhead ? lens[i] - s->overhead : 0);
-        slots += c == kSnapReject ? 0 : c;
-    }
-    if (slots && !digests) return rc_fail(RC_ERR_ARGUMENT, "null digests");
+    uint64_t slots;
+    if (int rc = check_lists(s, false, n, blobs, lens, data_digests, nullptr, counts, digests, status, slots)) return rc;
     std::lock_guard<std::mutex> lock(s->mu);
     rc::DeviceGuard guard(s->device);
     // blob i and its plaintext share an offset (16-aligned: AES-GCM's vector path)
@@ -404,47 +453,25 @@ int rc_snapshot_b64_device(rc_snapshot *s, uint64_t n, const uint8_t *const *d_t
         texts[i] = SnapText{reinterpret_cast<uint64_t>(d_texts[i]), text_lens[i] % 4 ? kSnapReject : text_lens[i],
                             reinterpret_cast<uint64_t>(d_out[i])};
     }
-    std::vector<SnapBlock> blocks;
-    list_blocks(n, uint64_t(kSnapThreads) * kSnapLaneChars, [&](uint64_t i) { return texts[i].len; }, blocks);
-    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const auto launch = [d_ok](const SnapText *t, const SnapBlock *b, uint64_t nb, hipStream_t st) {
+        return rc_snap_launch_b64(t, b, nb, d_ok, st);
+    };
     std::lock_guard<std::mutex> lock(s->mu);
     rc::DeviceGuard guard(s->device);
-    rc::SlotRing<rc_snapshot::Staging>::Slot *w = nullptr;
-    if (int rc = s->ring.acquire(w)) return rc;
-    const size_t block_off = up16(n * sizeof(SnapText));
-    const size_t stage = block_off + blocks.size() * sizeof(SnapBlock);
-    if (int rc = w->h_stage.ensure(stage)) return rc;
-    if (int rc = w->d_stage.ensure(stage)) return rc;
-    uint8_t *h = static_cast<uint8_t *>(w->h_stage.p);
-    uint8_t *d = static_cast<uint8_t *>(w->d_stage.p);
-    std::memcpy(h, texts.data(), n * sizeof(SnapText));
-    std::memcpy(h + block_off, blocks.data(), blocks.size() * sizeof(SnapBlock));
-    RC_HIP_TRY(hipMemcpyAsync(d, h, stage, hipMemcpyHostToDevice, st));
-    RC_HIP_TRY(hipMemsetAsync(d_ok, 1, n, st));
-    if (int rc = rc::timed(s->t_b64, st, [&] {
-            return rc_snap_launch_b64(reinterpret_cast<const SnapText *>(d),
-                                      reinterpret_cast<const SnapBlock *>(d + block_off), blocks.size(), d_ok, st);
-        }))
-        return rc;
-    return s->ring.finish(*w, st);
+    return bulk_locked(s, texts, uint64_t(kSnapThreads) * kSnapLaneChars, launch, kB64, d_ok,
+                       static_cast<hipStream_t>(hip_stream));
 }
 
 int rc_snapshot_timing_enable(rc_snapshot *s, int enable) {
     if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
-    return rc::timing_enable(s, {&s->t_crypt, &s->t_decode, &s->t_b64, &s->t_encode, &s->t_b64_encode, &s->t_seal,
-                                 &s->t_parts, &s->t_scan, &s->t_data, &s->t_find, &s->t_parse, &s->t_sums,
-                                 &s->t_strip},
-                             enable);
+    std::lock_guard<std::mutex> lock(s->mu);
+    for (rc::PairTimer &t : s->timers) t.enabled = enable != 0;
+    return RC_OK;
 }
 
 int rc_snapshot_timing_read(rc_snapshot *s, double *crypt_ms, double *decode_ms, double *b64_ms,
                             uint64_t *decode_calls) {
-    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
-    std::lock_guard<std::mutex> lock(s->mu);
-    rc::DeviceGuard guard(s->device);
-    if (int rc = s->t_crypt.read(crypt_ms, nullptr)) return rc;
-    if (int rc = s->t_b64.read(b64_ms, nullptr)) return rc;
-    return s->t_decode.read(decode_ms, decode_calls);
+    return read_timers(s, {{kCrypt, crypt_ms, nullptr}, {kB64, b64_ms, nullptr}, {kDecode, decode_ms, decode_calls}});
 }
 
 // ------------------------------------------------------------------------------------ writing
@@ -474,28 +501,10 @@ int rc_snapshot_b64_encode_device(rc_snapshot *s, uint64_t n, const uint8_t *con
             return rc_fail(RC_ERR_ARGUMENT, "buffer %llu: longer than 2^42 bytes", (unsigned long long)i);
         texts[i] = SnapText{reinterpret_cast<uint64_t>(d_in[i]), lens[i], reinterpret_cast<uint64_t>(d_out[i])};
     }
-    std::vector<SnapBlock> blocks;
-    list_blocks(n, uint64_t(kSnapThreads) * kSnapLaneBytes, [&](uint64_t i) { return texts[i].len; }, blocks);
-    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
     std::lock_guard<std::mutex> lock(s->mu);
     rc::DeviceGuard guard(s->device);
-    rc::SlotRing<rc_snapshot::Staging>::Slot *w = nullptr;
-    if (int rc = s->ring.acquire(w)) return rc;
-    const size_t block_off = up16(n * sizeof(SnapText));
-    const size_t stage = block_off + blocks.size() * sizeof(SnapBlock);
-    if (int rc = w->h_stage.ensure(stage)) return rc;
-    if (int rc = w->d_stage.ensure(stage)) return rc;
-    uint8_t *h = static_cast<uint8_t *>(w->h_stage.p);
-    uint8_t *d = static_cast<uint8_t *>(w->d_stage.p);
-    std::memcpy(h, texts.data(), n * sizeof(SnapText));
-    std::memcpy(h + block_off, blocks.data(), blocks.size() * sizeof(SnapBlock));
-    RC_HIP_TRY(hipMemcpyAsync(d, h, stage, hipMemcpyHostToDevice, st));
-    if (int rc = rc::timed(s->t_b64_encode, st, [&] {
-            return rc_snap_launch_b64_encode(reinterpret_cast<const SnapText *>(d),
-                                             reinterpret_cast<const SnapBlock *>(d + block_off), blocks.size(), st);
-        }))
-        return rc;
-    return s->ring.finish(*w, st);
+    return bulk_locked(s, texts, uint64_t(kSnapThreads) * kSnapLaneBytes, rc_snap_launch_b64_encode, kB64Encode, nullptr,
+                       static_cast<hipStream_t>(hip_stream));
 }
 
 int rc_snapshot_seal_tables_device(rc_snapshot *s, uint64_t n, const uint8_t *d_digests, const uint64_t *firsts,
@@ -580,12 +589,7 @@ int rc_snapshot_seal_tables_host(rc_snapshot *s, uint64_t n, const uint8_t *dige
 
 int rc_snapshot_write_timing_read(rc_snapshot *s, double *encode_ms, double *b64_ms, double *crypt_ms,
                                   uint64_t *encode_calls) {
-    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
-    std::lock_guard<std::mutex> lock(s->mu);
-    rc::DeviceGuard guard(s->device);
-    if (int rc = s->t_seal.read(crypt_ms, nullptr)) return rc;
-    if (int rc = s->t_b64_encode.read(b64_ms, nullptr)) return rc;
-    return s->t_encode.read(encode_ms, encode_calls);
+    return read_timers(s, {{kSeal, crypt_ms, nullptr}, {kB64Encode, b64_ms, nullptr}, {kEncode, encode_ms, encode_calls}});
 }
 
 // ------------------------------------------------------------------------------- writing `data`
@@ -616,7 +620,7 @@ int rc_snapshot_parts_device(rc_snapshot *s, uint64_t n, const uint64_t *d_chunk
         return RC_OK;
     }
     uint32_t *d_lo = static_cast<uint32_t *>(d_scratch);
-    return rc::timed(s->t_parts, st, [&] {
+    return rc::timed(s->timers[kParts], st, [&] {
         if (int rc = rc_snap_launch_part_count(d_chunk_ends, n, d_file_start, d_file_end, m, d_part_first, d_lo, st))
             return rc;
         if (int rc = rc_gc_launch_scan(d_part_first, m, d_part_first + m, st)) return rc;
@@ -637,7 +641,7 @@ int rc_snapshot_data_len_device(rc_snapshot *s, uint64_t n, uint64_t m, const ui
     const uint64_t groups = rc_snap_part_groups(capacity);
     std::lock_guard<std::mutex> lock(s->mu);
     rc::DeviceGuard guard(s->device);
-    return rc::timed(s->t_scan, st, [&] {
+    return rc::timed(s->timers[kScan], st, [&] {
         if (int rc = rc_gc_launch_scan(d_group_len, groups, d_group_len + groups, st)) return rc;
         if (int rc = rc_gc_launch_scan(d_piece_len, m + 1, d_piece_len + m + 1, st)) return rc;
         return rc_snap_launch_piece_offsets(d_part_first, m, d_records, capacity, d_group_len, d_piece_len,
@@ -658,7 +662,7 @@ int rc_snapshot_encode_data_device(rc_snapshot *s, uint64_t n, uint64_t m, const
     const hipStream_t st = static_cast<hipStream_t>(hip_stream);
     std::lock_guard<std::mutex> lock(s->mu);
     rc::DeviceGuard guard(s->device);
-    return rc::timed(s->t_data, st, [&] {
+    return rc::timed(s->timers[kData], st, [&] {
         if (int rc = rc_snap_launch_encode_data(d_records, d_part_first + m, capacity, d_group_off, d_piece_pre, d_text,
                                                 st))
             return rc;
@@ -669,12 +673,7 @@ int rc_snapshot_encode_data_device(rc_snapshot *s, uint64_t n, uint64_t m, const
 
 int rc_snapshot_data_timing_read(rc_snapshot *s, double *parts_ms, double *scan_ms, double *encode_ms,
                                  uint64_t *encode_calls) {
-    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
-    std::lock_guard<std::mutex> lock(s->mu);
-    rc::DeviceGuard guard(s->device);
-    if (int rc = s->t_parts.read(parts_ms, nullptr)) return rc;
-    if (int rc = s->t_scan.read(scan_ms, nullptr)) return rc;
-    return s->t_data.read(encode_ms, encode_calls);
+    return read_timers(s, {{kParts, parts_ms, nullptr}, {kScan, scan_ms, nullptr}, {kData, encode_ms, encode_calls}});
 }
 
 // ------------------------------------------------------------------------------- reading `data`
@@ -711,24 +710,15 @@ int rc_snapshot_find_parts_device(rc_snapshot *s, uint64_t n, const uint8_t *con
     const hipStream_t st = static_cast<hipStream_t>(hip_stream);
     std::lock_guard<std::mutex> lock(s->mu);
     rc::DeviceGuard guard(s->device);
-    rc::SlotRing<rc_snapshot::Staging>::Slot *w = nullptr;
-    if (int rc = s->ring.acquire(w)) return rc;
     // SnapParseText[n] | SnapBlock[]; the workgroup counts: parts[nb + 1] | first parts[nb + 1]
-    const size_t block_off = up16(n * sizeof(SnapParseText));
-    const size_t stage = block_off + nb * sizeof(SnapBlock);
-    if (int rc = w->h_stage.ensure(stage)) return rc;
-    if (int rc = w->d_stage.ensure(stage)) return rc;
-    if (int rc = w->d_scratch.ensure(2 * (nb + 1) * sizeof(uint64_t))) return rc;
-    uint8_t *h = static_cast<uint8_t *>(w->h_stage.p);
-    uint8_t *d = static_cast<uint8_t *>(w->d_stage.p);
-    std::memcpy(h, texts.data(), n * sizeof(SnapParseText));
-    std::memcpy(h + block_off, blocks.data(), nb * sizeof(SnapBlock));
-    RC_HIP_TRY(hipMemcpyAsync(d, h, stage, hipMemcpyHostToDevice, st));
-    RC_HIP_TRY(hipMemcpyAsync(d_desc, d, n * sizeof(SnapParseText), hipMemcpyDeviceToDevice, st));
-    const SnapParseText *dt = reinterpret_cast<const SnapParseText *>(d);
-    const SnapBlock *db = reinterpret_cast<const SnapBlock *>(d + block_off);
-    uint64_t *part_counts = static_cast<uint64_t *>(w->d_scratch.p), *first_counts = part_counts + nb + 1;
-    if (int rc = rc::timed(s->t_find, st, [&] {
+    Staged g;
+    if (int rc = stage_lists(s, {texts, blocks}, st, g)) return rc;
+    if (int rc = g.w->d_scratch.ensure(2 * (nb + 1) * sizeof(uint64_t))) return rc;
+    const SnapParseText *dt = g.list<SnapParseText>(0);
+    const SnapBlock *db = g.list<SnapBlock>(1);
+    RC_HIP_TRY(hipMemcpyAsync(d_desc, dt, n * sizeof(SnapParseText), hipMemcpyDeviceToDevice, st));
+    uint64_t *part_counts = static_cast<uint64_t *>(g.w->d_scratch.p), *first_counts = part_counts + nb + 1;
+    if (int rc = rc::timed(s->timers[kFind], st, [&] {
             if (int rc = rc_snap_launch_find(false, dt, n, db, nb, part_counts, first_counts, capacity, d_records,
                                              d_text_first, d_text_run_first, d_run_part_first, st))
                 return rc;
@@ -738,7 +728,7 @@ int rc_snapshot_find_parts_device(rc_snapshot *s, uint64_t n, const uint8_t *con
                                        d_text_run_first, d_run_part_first, st);
         }))
         return rc;
-    return s->ring.finish(*w, st);
+    return s->ring.finish(*g.w, st);
 }
 
 namespace {
@@ -767,7 +757,7 @@ int rc_snapshot_parse_parts_device(rc_snapshot *s, uint64_t n, const void *d_des
     std::lock_guard<std::mutex> lock(s->mu);
     rc::DeviceGuard guard(s->device);
     RC_HIP_TRY(hipMemsetAsync(d_status, RC_PARTS_OK, n, st));
-    return rc::timed(s->t_parse, st, [&] {
+    return rc::timed(s->timers[kParse], st, [&] {
         return rc_snap_launch_parse(static_cast<const SnapParseText *>(d_desc), n, d_text_first, d_text_run_first,
                                     capacity, d_records, d_run_off, d_run_end, d_run_part_first, d_status, st);
     });
@@ -790,7 +780,7 @@ int rc_snapshot_part_sums_device(rc_snapshot *s, uint64_t n, uint64_t capacity, 
     std::lock_guard<std::mutex> lock(s->mu);
     rc::DeviceGuard guard(s->device);
     if (!d_order) RC_HIP_TRY(hipMemsetAsync(d_run_sorted, 1, capacity, st));
-    return rc::timed(s->t_sums, st, [&] {
+    return rc::timed(s->timers[kSums], st, [&] {
         if (int rc = rc_snap_launch_size_sums(d_records, d_order, d_text_first + n, capacity, d_group, d_excl, st))
             return rc;
         if (int rc = rc_gc_launch_scan(d_group, groups, d_group + groups, st)) return rc;
@@ -817,7 +807,7 @@ int rc_snapshot_strip_parts_device(rc_snapshot *s, uint64_t n, const void *d_des
     std::lock_guard<std::mutex> lock(s->mu);
     rc::DeviceGuard guard(s->device);
     RC_HIP_TRY(hipMemsetAsync(d_stripped_len, 0, n * sizeof(uint64_t), st));
-    return rc::timed(s->t_strip, st, [&] {
+    return rc::timed(s->timers[kStrip], st, [&] {
         if (int rc = rc_snap_launch_run_len(d_run_off, d_run_end, d_text_run_first + n, capacity, d_local, d_group, st))
             return rc;
         if (int rc = rc_gc_launch_scan(d_group, groups, d_group + groups, st)) return rc;
@@ -828,13 +818,8 @@ int rc_snapshot_strip_parts_device(rc_snapshot *s, uint64_t n, const void *d_des
 
 int rc_snapshot_read_timing_read(rc_snapshot *s, double *find_ms, double *parse_ms, double *sums_ms, double *strip_ms,
                                  uint64_t *find_calls) {
-    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
-    std::lock_guard<std::mutex> lock(s->mu);
-    rc::DeviceGuard guard(s->device);
-    if (int rc = s->t_parse.read(parse_ms, nullptr)) return rc;
-    if (int rc = s->t_sums.read(sums_ms, nullptr)) return rc;
-    if (int rc = s->t_strip.read(strip_ms, nullptr)) return rc;
-    return s->t_find.read(find_ms, find_calls);
+    return read_timers(s, {{kParse, parse_ms, nullptr}, {kSums, sums_ms, nullptr}, {kStrip, strip_ms, nullptr},
+                           {kFind, find_ms, find_calls}});
 }
 
 }  // extern "C"

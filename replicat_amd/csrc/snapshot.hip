@@ -28,15 +28,9 @@
 // has none.  The wipe of a table whose tag failed is restore.hip's verdict kernel, unchanged.
 #include <hip/hip_runtime.h>
 
-#include "capi_internal.h"
-#include "snapshot_kernels.h"
+#include "snapshot_device.h"
 
 namespace {
-
-#define GLOBAL __attribute__((address_space(1)))
-typedef GLOBAL uint8_t *gbytes;
-typedef const GLOBAL uint8_t *gcbytes;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t kTableSpan = kSnapThreads * kSnapMaxStride;       // text of one workgroup
 constexpr uint32_t kTableLds = (kTableSpan + 15 + 8 + 15) / 16 * 16;  // + skew + a lane's look-ahead
@@ -77,17 +71,6 @@ __device__ __forceinline__ uint32_t b64_group(uint32_t chars, uint32_t pad, bool
     // pad == 1: the third byte has only unused bits; pad == 2: the second and third
     bad |= (pad >= 1 && (t & 0xFFu)) || (pad == 2 && (t & 0xFF00u));
     return t;
-}
-
-// Copies the aligned 16-byte granules that hold [p, p + len) into lds; byte k of the span is
-// lds[skew + k] afterwards (after the caller's barrier).
-__device__ __forceinline__ uint32_t stage_span(uint8_t *lds, gcbytes p, uint32_t len) {
-    const uint32_t skew = uint32_t(reinterpret_cast<uintptr_t>(p) & 15);
-    const GLOBAL u32x4 *src = reinterpret_cast<const GLOBAL u32x4 *>(p - skew);
-    u32x4 *dst = reinterpret_cast<u32x4 *>(lds);
-    const uint32_t granules = (skew + len + 15) >> 4;
-    for (uint32_t k = threadIdx.x; k < granules; k += kSnapThreads) dst[k] = src[k];
-    return skew;
 }
 
 // One atomic that makes the verdict byte at p `value` when the byte can only move one way:
@@ -238,19 +221,18 @@ __global__ __launch_bounds__(kSnapThreads) void rc_snap_b64_kernel(const SnapTex
 
 int rc_snap_launch_tables(const SnapTable *d_tables, const SnapBlock *d_blocks, uint64_t n_blocks,
                           uint32_t digest_bytes, uint8_t *d_slots, uint8_t *d_status, hipStream_t stream) {
-    if (!n_blocks) return 0;
-    if (n_blocks > 0x7FFFFFFFull)
-        return rc_fail(RC_ERR_ARGUMENT, "%llu workgroups of records in one call", (unsigned long long)n_blocks);
-    rc_snap_tables_kernel<<<static_cast<unsigned>(n_blocks), kSnapThreads, 0, stream>>>(d_tables, d_blocks, digest_bytes,
-                                                                                    d_slots, d_status);
+    unsigned grid;
+    if (int rc = grid_of(n_blocks, 1, "records", grid)) return rc;
+    if (!grid) return 0;
+    rc_snap_tables_kernel<<<grid, kSnapThreads, 0, stream>>>(d_tables, d_blocks, digest_bytes, d_slots, d_status);
     return rc::launch_status("rc_snap_tables_kernel");
 }
 
 int rc_snap_launch_b64(const SnapText *d_texts, const SnapBlock *d_blocks, uint64_t n_blocks, uint8_t *d_ok,
                        hipStream_t stream) {
-    if (!n_blocks) return 0;
-    if (n_blocks > 0x7FFFFFFFull)
-        return rc_fail(RC_ERR_ARGUMENT, "%llu workgroups of text in one call", (unsigned long long)n_blocks);
-    rc_snap_b64_kernel<<<static_cast<unsigned>(n_blocks), kSnapThreads, 0, stream>>>(d_texts, d_blocks, d_ok);
+    unsigned grid;
+    if (int rc = grid_of(n_blocks, 1, "text", grid)) return rc;
+    if (!grid) return 0;
+    rc_snap_b64_kernel<<<grid, kSnapThreads, 0, stream>>>(d_texts, d_blocks, d_ok);
     return rc::launch_status("rc_snap_b64_kernel");
 }

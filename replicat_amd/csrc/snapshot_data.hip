@@ -31,14 +31,9 @@
 //   place    one wave per fixed piece: a byte copy to its offset.
 #include <hip/hip_runtime.h>
 
-#include "capi_internal.h"
-#include "snapshot_kernels.h"
+#include "snapshot_device.h"
 
 namespace {
-
-#define GLOBAL __attribute__((address_space(1)))
-typedef GLOBAL uint8_t *gbytes;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t kRunPad = 32;  // >= 15 + 16: two runs never share a granule, whatever their skews
 constexpr uint32_t kDataLds = (kSnapThreads * (kSnapPartMaxLen + kRunPad) + 16 + 15) / 16 * 16;
@@ -46,34 +41,6 @@ constexpr uint32_t kRelMask = 0xFFFFu;       // rel < 256 * 74
 constexpr uint32_t kLastPart = 0x80000000u;  // in the rel word: the last part of its file
 static_assert(kSnapThreads * kSnapPartMaxLen <= kRelMask, "rel fits 16 bits");
 static_assert(kSnapThreads <= 256, "a run's number fits a byte");
-
-// The first k in [0, n) with a[k] >= x (or > x), n if none.
-__device__ __forceinline__ uint64_t bound(const uint64_t *a, uint64_t n, uint64_t x, bool upper) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        const uint64_t v = a[mid];
-        if (upper ? v <= x : v < x)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
-// Exclusive prefix of v over the workgroup's lanes, and the sum; lds holds kSnapThreads words.
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t *lds, uint32_t &total) {
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 1; off < kSnapThreads; off <<= 1) {  // inclusive Hillis-Steele scan
-        const uint32_t x = int(threadIdx.x) >= off ? lds[threadIdx.x - off] : 0;
-        __syncthreads();
-        lds[threadIdx.x] += x;
-        __syncthreads();
-    }
-    total = lds[kSnapThreads - 1];
-    return lds[threadIdx.x] - v;
-}
 
 template <int N>
 __device__ __forceinline__ uint32_t put_text(uint8_t *lds, uint32_t at, const char (&s)[N]) {
@@ -245,17 +212,6 @@ __global__ __launch_bounds__(kSnapThreads) void rc_snap_place_pieces_kernel(cons
     uint8_t *dst = text + piece_off[j];
     for (uint64_t k = threadIdx.x & 63; k < len; k += 64) dst[k] = src[k];
 }
-
-namespace {
-
-int grid_of(uint64_t items, uint64_t per, const char *what, unsigned &grid) {
-    const uint64_t g = (items + per - 1) / per;
-    if (g > 0x7FFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "%llu workgroups of %s in one call", (unsigned long long)g, what);
-    grid = static_cast<unsigned>(g);
-    return 0;
-}
-
-}  // namespace
 
 int rc_snap_launch_part_count(const uint64_t *d_ends, uint64_t n, const uint64_t *d_file_start,
                               const uint64_t *d_file_end, uint64_t m, uint64_t *d_counts, uint32_t *d_lo,

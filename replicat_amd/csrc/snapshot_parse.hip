@@ -27,13 +27,9 @@
 //            the stripped text.
 #include <hip/hip_runtime.h>
 
-#include "capi_internal.h"
-#include "snapshot_kernels.h"
+#include "snapshot_device.h"
 
 namespace {
-
-#define GLOBAL __attribute__((address_space(1)))
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // {"range":[ and "chunks":[ as little-endian words: bytes 0-3, 4-7 and 8-9
 constexpr uint32_t kPart0 = 0x6172227Bu, kPart1 = 0x2265676Eu, kPart2 = 0x5B3Au;
@@ -42,34 +38,6 @@ constexpr uint32_t kList0 = 0x75686322u, kList1 = 0x22736B6Eu, kList2 = 0x5B3Au;
 // The word at byte j of the window w (j is a constant once the caller's loop is unrolled).
 __device__ __forceinline__ uint32_t word_at(const uint32_t (&w)[12], int j) {
     return __funnelshift_r(w[j >> 2], w[(j >> 2) + 1], 8 * (j & 3));
-}
-
-// Exclusive prefix of v over the workgroup's lanes, and the sum; lds holds kSnapThreads words.
-template <class T>
-__device__ __forceinline__ T block_scan(T v, T *lds, T &total) {
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 1; off < kSnapThreads; off <<= 1) {  // inclusive Hillis-Steele scan
-        const T x = int(threadIdx.x) >= off ? lds[threadIdx.x - off] : T(0);
-        __syncthreads();
-        lds[threadIdx.x] += x;
-        __syncthreads();
-    }
-    total = lds[kSnapThreads - 1];
-    return lds[threadIdx.x] - v;
-}
-
-// The last k in [0, n] with a[k] <= x, for a non-decreasing a[0 .. n] with a[0] <= x.
-__device__ __forceinline__ uint64_t owner_of(const uint64_t *a, uint64_t n, uint64_t x) {
-    uint64_t lo = 0, hi = n + 1;  // the first k with a[k] > x, n + 1 if none
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] <= x)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo - 1;
 }
 
 // The bytes of one text, read as aligned words that each hold at least one of them; 0 past the end.
@@ -402,17 +370,6 @@ __global__ __launch_bounds__(kSnapThreads) void rc_snap_strip_kernel(const SnapP
             stripped_len[i] = t.len - removed;
     }
 }
-
-namespace {
-
-int grid_of(uint64_t items, uint64_t per, const char *what, unsigned &grid) {
-    const uint64_t g = (items + per - 1) / per;
-    if (g > 0x7FFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "%llu workgroups of %s in one call", (unsigned long long)g, what);
-    grid = static_cast<unsigned>(g);
-    return 0;
-}
-
-}  // namespace
 
 int rc_snap_launch_find(bool scatter, const SnapParseText *d_texts, uint64_t n_texts, const SnapBlock *d_blocks,
                         uint64_t n_blocks, uint64_t *d_part_counts, uint64_t *d_first_counts, uint64_t capacity,

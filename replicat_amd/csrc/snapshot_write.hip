@@ -25,15 +25,9 @@
 //           leaves the pages of the buffer).
 #include <hip/hip_runtime.h>
 
-#include "capi_internal.h"
-#include "snapshot_kernels.h"
+#include "snapshot_device.h"
 
 namespace {
-
-#define GLOBAL __attribute__((address_space(1)))
-typedef GLOBAL uint8_t *gbytes;
-typedef const GLOBAL uint8_t *gcbytes;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t kRecordWords = (kSnapMaxStride + 3) / 4;                 // 25
 constexpr uint32_t kMaxGroups = (kSnapMaxStride - 10) / 4;                   // 22 for L = 64
@@ -99,17 +93,6 @@ __device__ __forceinline__ void store_span(gbytes base, const uint8_t *lds, uint
                 if (k >= skew && k < end) base[k] = lds[k];
         }
     }
-}
-
-// Copies the aligned 16-byte granules that hold [p, p + len) into lds; byte k of the span is
-// lds[skew + k] afterwards (after the caller's barrier).
-__device__ __forceinline__ uint32_t stage_span(uint8_t *lds, gcbytes p, uint32_t len) {
-    const uint32_t skew = uint32_t(reinterpret_cast<uintptr_t>(p) & 15);
-    const GLOBAL u32x4 *src = reinterpret_cast<const GLOBAL u32x4 *>(p - skew);
-    u32x4 *dst = reinterpret_cast<u32x4 *>(lds);
-    const uint32_t granules = (skew + len + 15) >> 4;
-    for (uint32_t k = threadIdx.x; k < granules; k += kSnapThreads) dst[k] = src[k];
-    return skew;
 }
 
 }  // namespace
@@ -234,19 +217,18 @@ __global__ __launch_bounds__(kSnapThreads) void rc_snap_b64_encode_kernel(const 
 
 int rc_snap_launch_encode_tables(const SnapTable *d_tables, const SnapBlock *d_blocks, uint64_t n_blocks,
                                  uint32_t digest_bytes, const uint8_t *d_slots, hipStream_t stream) {
-    if (!n_blocks) return 0;
-    if (n_blocks > 0x7FFFFFFFull)
-        return rc_fail(RC_ERR_ARGUMENT, "%llu workgroups of records in one call", (unsigned long long)n_blocks);
-    rc_snap_encode_tables_kernel<<<static_cast<unsigned>(n_blocks), kSnapThreads, 0, stream>>>(d_tables, d_blocks,
-                                                                                           digest_bytes, d_slots);
+    unsigned grid;
+    if (int rc = grid_of(n_blocks, 1, "records", grid)) return rc;
+    if (!grid) return 0;
+    rc_snap_encode_tables_kernel<<<grid, kSnapThreads, 0, stream>>>(d_tables, d_blocks, digest_bytes, d_slots);
     return rc::launch_status("rc_snap_encode_tables_kernel");
 }
 
 int rc_snap_launch_b64_encode(const SnapText *d_texts, const SnapBlock *d_blocks, uint64_t n_blocks,
                               hipStream_t stream) {
-    if (!n_blocks) return 0;
-    if (n_blocks > 0x7FFFFFFFull)
-        return rc_fail(RC_ERR_ARGUMENT, "%llu workgroups of bytes in one call", (unsigned long long)n_blocks);
-    rc_snap_b64_encode_kernel<<<static_cast<unsigned>(n_blocks), kSnapThreads, 0, stream>>>(d_texts, d_blocks);
+    unsigned grid;
+    if (int rc = grid_of(n_blocks, 1, "bytes", grid)) return rc;
+    if (!grid) return 0;
+    rc_snap_b64_encode_kernel<<<grid, kSnapThreads, 0, stream>>>(d_texts, d_blocks);
     return rc::launch_status("rc_snap_b64_encode_kernel");
 }

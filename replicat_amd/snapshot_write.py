@@ -28,24 +28,22 @@ Out of scope: uploading the file to a backend and the cache.  There is no CPU fa
 device work: without the HIP library or a GPU, construction raises ``ChunkerUnavailable``.
 """
 import base64
-import ctypes
 import hashlib
 import json
 import os
-from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
 from typing import Any, Callable, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import RC_CIPHER_AES_GCM, RC_CIPHER_CHACHA20_POLY1305, RC_CIPHER_NONE, check, lib
-from .chunker import _current_device, _ptr_array
-from .hashing import SLOT, hasher_from_config, hashlib_from_config, state_init
+from ._lib import check, lib
+from .chunker import _ptr_array
+from .hashing import SLOT
 from .naming import ChunkNaming, snapshot_location
-from .pipeline import ChunkEncryption, DeviceSnapshotProducer, hashing_arguments
-from .snapshots import _ENC_HEAD, _ENC_MID, _ENC_TAIL, _PLAIN_MID, _Buffers, _up, serialize, type_hint
+from .pipeline import ChunkEncryption
+from .snapshots import (ALIGN, _ENC_HEAD, _ENC_MID, _ENC_TAIL, _PLAIN_HEAD, _PLAIN_MID, _offsets, _SnapshotHandle,
+                        serialize, type_hint)
 
-_PLAIN_HEAD = b'{"chunks":'
 NONCE_PREFIX = 64   # bytes of a table's text an injected nonce rule is shown
 SMALL_PIECE = 4096  # fixed parts shorter than this are placed by one scatter
 
@@ -193,7 +191,7 @@ class WrittenSnapshot:
     digest: bytes
 
 
-class GpuSnapshotWriter:
+class GpuSnapshotWriter(_SnapshotHandle):
     """Snapshot bodies of one repository, sealed on one HIP device.  ``encryption``, ``userkey``,
     ``hashing`` / ``digest_size`` / ``hash_bits``, ``device`` and ``host_digest_min`` are
     ``GpuSnapshotLoader``'s; ``naming`` names the file.  ``nonces(message_or_prefix, key)`` returns
@@ -201,119 +199,37 @@ class GpuSnapshotWriter:
     first 64 bytes of a table's text and its subkey.  The default is ``os.urandom`` per message, as
     the reference's adapter (adapters.py:131-134); an injected rule costs one synchronisation per
     call, because subkeys are then derived on the host as well."""
+    _ALWAYS_HASHES = True  # the file's own digest
+    _THREAD_PREFIX = 'snapshot-write-digest'
+    _STATS = ('snapshots', 'bytes_uploaded', 'bytes_copied_back', 'data_digests_host', 'data_digests_device',
+              'file_digests_host', 'file_digests_device', 'data_syncs')
 
     def __init__(self, *, encryption: Optional[ChunkEncryption], userkey: Optional[bytes] = None,
                  hashing='blake2b', digest_size=None, hash_bits=None, device=None,
                  host_digest_min: Optional[int] = None, naming: Optional[ChunkNaming] = None,
                  nonces: Optional[Callable[[bytes, bytes], bytes]] = None):
-        digest_size, hash_bits, hash_args = hashing_arguments(hashing, digest_size, hash_bits)
-        self.hashing, self.hash_bits, self.digest_size = hashing, hash_bits, digest_size
-        self._hashlib_args = ({'length': digest_size} if hashing == 'blake2b' else {'bits': hash_bits})
-        self.encryption = encryption
-        self.encrypted = encryption is not None
-        self.userkey = None if userkey is None else bytes(userkey)
-        if self.encrypted and self.userkey is None:
+        if encryption is not None and userkey is None:  # before any device is touched
             raise ValueError('an encrypted repository needs the user key to seal `data`')
         self.naming = ChunkNaming() if naming is None else naming
         self.nonces = nonces
-        self.host_digest_min = (DeviceSnapshotProducer.HOST_DIGEST_MIN_BY_HASH[hashing, hash_bits]
-                                if host_digest_min is None else int(host_digest_min))
-        self._h = None
-        self.device = int(_current_device() if device is None else device)
-        handle = ctypes.c_void_p()
-        # the handles first: without a GPU this is where ChunkerUnavailable is raised
-        self.hasher = hasher_from_config(hashing, device=self.device, **hash_args)
-        if self.encrypted:
-            self.cipher = encryption.make_cipher(self.device)
-            if len(self.userkey) != self.cipher.key_bytes:
-                raise ValueError('Invalid key size')
-            kdf = state_init(self.cipher.key_bytes, key=encryption.shared_key,
-                             salt=encryption.shared_kdf_params)
-            code = (RC_CIPHER_CHACHA20_POLY1305 if encryption.cipher == 'chacha20_poly1305'
-                    else RC_CIPHER_AES_GCM)
-            check(lib().rc_snapshot_create(digest_size, code, self.cipher.handle(), kdf, self.device,
-                                           ctypes.byref(handle)))
-        else:
-            self.cipher = None
-            check(lib().rc_snapshot_create(digest_size, RC_CIPHER_NONE, None, None, self.device,
-                                           ctypes.byref(handle)))
-        self._h = handle
-        self.overhead = int(lib().rc_snapshot_overhead(handle))
-        self.stride = int(lib().rc_snapshot_stride(handle))
-        import torch
-        self._torch = torch
-        self.dev = torch.device('cuda', self.device)
-        self._stream = torch.cuda.Stream(device=self.dev)
-        self._buf = _Buffers(torch, self.dev)
-        self._pool = None
-        self.stats = dict.fromkeys(('snapshots', 'bytes_uploaded', 'bytes_copied_back', 'data_digests_host',
-                                    'data_digests_device', 'file_digests_host', 'file_digests_device', 'data_syncs'), 0)
-
-    def close(self):
-        """Release the native handles and the buffers (the object is unusable after)."""
-        h, self._h = getattr(self, '_h', None), None
-        if h:
-            lib().rc_snapshot_destroy(h)  # before the cipher it borrows
-        self._buf = None
-        pool, self._pool = getattr(self, '_pool', None), None
-        if pool is not None:
-            pool.shutdown(wait=True)
-        for name in ('cipher', 'hasher'):
-            obj = getattr(self, name, None)
-            if obj is not None:
-                obj.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    # ---------------------------------------------------------------------- profiling
-
-    def timing(self, enable: bool):
-        check(lib().rc_snapshot_timing_enable(self._h, 1 if enable else 0))
+        super().__init__(encryption=encryption, userkey=userkey, hashing=hashing, digest_size=digest_size,
+                         hash_bits=hash_bits, device=device, host_digest_min=host_digest_min)
 
     def timing_read(self) -> dict:
         """Summed kernel milliseconds since the last read: table encode, bulk base64 encode,
         subkeys + encryption of the tables."""
-        ms = [ctypes.c_double() for _ in range(3)]
-        calls = ctypes.c_uint64()
-        check(lib().rc_snapshot_write_timing_read(self._h, *(ctypes.byref(m) for m in ms), ctypes.byref(calls)))
-        return {'encode_ms': ms[0].value, 'b64_ms': ms[1].value, 'crypt_ms': ms[2].value,
-                'encode_calls': calls.value}
+        return self._read_timers('rc_snapshot_write_timing_read', ('encode_ms', 'b64_ms', 'crypt_ms'), 'encode_calls')
 
     def data_timing_read(self) -> dict:
         """Summed kernel milliseconds of the three stages of `data` since the last read: parts,
         scans and offsets, text."""
-        ms = [ctypes.c_double() for _ in range(3)]
-        calls = ctypes.c_uint64()
-        check(lib().rc_snapshot_data_timing_read(self._h, *(ctypes.byref(m) for m in ms), ctypes.byref(calls)))
-        return {'parts_ms': ms[0].value, 'scan_ms': ms[1].value, 'data_encode_ms': ms[2].value,
-                'data_encode_calls': calls.value}
+        return self._read_timers('rc_snapshot_data_timing_read', ('parts_ms', 'scan_ms', 'data_encode_ms'),
+                                 'data_encode_calls')
 
     # ------------------------------------------------------------------------ helpers
 
     def table_len(self, count: int) -> int:
         return int(lib().rc_snapshot_table_len(self._h, int(count)))
-
-    def _hash(self, data) -> bytes:
-        h = hashlib_from_config(self.hashing, **self._hashlib_args)
-        h.update(data)
-        return h.digest()
-
-    def _threads(self):
-        if self._pool is None:
-            self._pool = ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1),
-                                            thread_name_prefix='snapshot-write-digest')
-        return self._pool
 
     def _rows(self, chunks):
         """``chunks`` as an (n, L) uint8 array or a ``DeviceDigests``; ValueError for a digest of
@@ -350,8 +266,7 @@ class GpuSnapshotWriter:
         for: a call with at least one ``SnapshotData`` copies the lengths back and synchronises
         once before anything else is enqueued (``stats['data_syncs']``), and with an injected
         nonce rule, which is shown the text, copies the texts back before it encrypts them."""
-        if not self._h:
-            raise RuntimeError('GpuSnapshotWriter is closed')
+        self._live()
         items = list(items)
         for _, data in items:  # refused before anything is enqueued
             if isinstance(data, SnapshotData):
@@ -456,8 +371,7 @@ class GpuSnapshotWriter:
         """The parts of the files of `layout`, as stage 1 finds them: ``part_first`` (m + 1; the
         parts of file f are the rows part_first[f] .. part_first[f + 1] - 1, in counter order) and,
         per part, ``file``, ``chunk``, ``start``, ``end``, ``index`` and ``counter``."""
-        if not self._h:
-            raise RuntimeError('GpuSnapshotWriter is closed')
+        self._live()
         layout.validate(counter0)
         names = ('file', 'chunk', 'start', 'end', 'index', 'counter')
         if layout.n == 0 or layout.m == 0:
@@ -475,20 +389,6 @@ class GpuSnapshotWriter:
         return out
 
     # ------------------------------------------------------------------- device stages
-
-    def _pinned_to_device(self, name, pieces, total):
-        """pieces: (offset, uint8 array or bytes) into one pinned image, copied to the device
-        buffer of the same name on the writer's stream.  Returns the device tensor."""
-        h = self._buf.get('h_' + name, max(total, 16), pinned=True)
-        d = self._buf.get('d_' + name, max(total, 16))
-        h_np = h.numpy()
-        for off, data in pieces:
-            view = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.reshape(-1)
-            h_np[off:off + view.size] = view
-        if total:
-            d[:total].copy_(h[:total], non_blocking=True)
-        self.stats['bytes_uploaded'] += total
-        return d
 
     def _slots(self, prepared, order):
         """The digests of the host-given tables as 64-byte slots in one device buffer.  Returns
@@ -539,14 +439,11 @@ class GpuSnapshotWriter:
         one scatter, long ones (a long ``serialize(data)``) by a copy each."""
         torch = self._torch
         small = [(o, p) for o, p in pieces if len(p) < SMALL_PIECE]
-        at, big = 0, []  # (offset in the upload image, offset in the file image, bytes)
-        for o, p in pieces:
-            if len(p) >= SMALL_PIECE:
-                big.append((at, o, p))
-                at += _up(len(p))
+        big = [(o, p) for o, p in pieces if len(p) >= SMALL_PIECE]
         if big:
-            d = self._pinned_to_device('big', [(a, p) for a, _, p in big], at)
-            for a, o, p in big:
+            ats, size = _offsets(len(p) for _, p in big)  # in the upload image
+            d = self._upload('big', [(a, p) for a, (_, p) in zip(ats, big)], size)
+            for a, (o, p) in zip(ats, big):
                 d_file[o:o + len(p)].copy_(d[a:a + len(p)], non_blocking=True)
         if small:
             lens = np.fromiter((len(p) for _, p in small), dtype=np.int64, count=len(small))
@@ -555,7 +452,7 @@ class GpuSnapshotWriter:
             starts = np.concatenate([[0], np.cumsum(lens)[:-1]])
             idx = np.repeat(offs - starts, lens) + np.arange(m, dtype=np.int64)
             packed = b''.join(p for _, p in small)
-            d = self._pinned_to_device('small', [(0, idx.view(np.uint8)), (8 * m, packed)], 9 * m)
+            d = self._upload('small', [(0, idx.view(np.uint8)), (8 * m, packed)], 9 * m)
             d_file.index_put_((d[:8 * m].view(torch.int64),), d[8 * m:9 * m])
 
     def _file_digests(self, d_file, offs, lens, want):
@@ -597,40 +494,47 @@ class GpuSnapshotWriter:
             self.stats['file_digests_host'] += len(big)
         return contents, digests
 
-    def _run_plain(self, prepared, file_digests):
-        torch = self._torch
-        n = len(prepared)
-        order = sorted(range(n), key=lambda i: isinstance(prepared[i][0], DeviceDigests))
-        with torch.cuda.stream(self._stream):
-            bases, firsts, counts = self._slots(prepared, order)
-            tlen = [self.table_len(counts[i]) for i in order]
-            lens = [len(_PLAIN_HEAD) + t + len(_PLAIN_MID) + _text_len(prepared[i][1]) + 1 for t, i in zip(tlen, order)]
-            offs, total = [], 0
-            for ln in lens:
-                offs.append(total)
-                total += _up(ln)
-            d_file = self._buf.get('d_file', max(total, 16))
-            fp = d_file.data_ptr()
-            self._seal(order, bases, firsts, counts, 0, 0, [fp + o + len(_PLAIN_HEAD) for o in offs], None)
-            pieces = []
-            for o, t, ln, i in zip(offs, tlen, lens, order):
-                pieces.append((o, _PLAIN_HEAD))
-                text = prepared[i][1]
-                if isinstance(text, _DataPlan):  # straight into the file image
-                    pieces += [(o + len(_PLAIN_HEAD) + t, _PLAIN_MID), (o + ln - 1, b'}')]
-                    self._encode_data(text, fp + o + len(_PLAIN_HEAD) + t + len(_PLAIN_MID))
-                else:
-                    pieces.append((o + len(_PLAIN_HEAD) + t, _PLAIN_MID + text + b'}'))
-            self._place(d_file, pieces)
-            small, h_fd = self._file_digests(d_file, offs, lens, file_digests)
-            contents, digests = self._finish(d_file, offs, lens, total, small, h_fd, file_digests)
-        back = [None] * n
+    def _emit(self, lens, order, want, fill):
+        """The end of a run: the files of ``lens`` bytes get 16-aligned offsets in one device
+        image; ``fill(address of the image, offsets)`` enqueues what writes into it and returns
+        the fixed pieces, which are placed; then the digests, the copy back, and the contents
+        and digests returned to the order of the items (file k is item ``order[k]``)."""
+        offs, total = _offsets(lens)
+        d_file = self._buf.get('d_file', max(total, ALIGN))
+        self._place(d_file, fill(d_file.data_ptr(), offs))
+        small, h_fd = self._file_digests(d_file, offs, lens, want)
+        contents, digests = self._finish(d_file, offs, lens, total, small, h_fd, want)
+        back = [None] * len(order)
         for k, i in enumerate(order):
             back[i] = (contents[k], digests[k])
         return [b[0] for b in back], [b[1] for b in back]
 
+    def _run_plain(self, prepared, file_digests):
+        n = len(prepared)
+        order = sorted(range(n), key=lambda i: isinstance(prepared[i][0], DeviceDigests))
+        head, mid = len(_PLAIN_HEAD), len(_PLAIN_MID)
+        with self._torch.cuda.stream(self._stream):
+            bases, firsts, counts = self._slots(prepared, order)
+            tlen = [self.table_len(counts[i]) for i in order]
+            lens = [head + t + mid + _text_len(prepared[i][1]) + 1 for t, i in zip(tlen, order)]
+
+            def fill(fp, offs):
+                self._seal(order, bases, firsts, counts, 0, 0, [fp + o + head for o in offs], None)
+                pieces = []
+                for o, t, ln, i in zip(offs, tlen, lens, order):
+                    pieces.append((o, _PLAIN_HEAD))
+                    text = prepared[i][1]
+                    if isinstance(text, _DataPlan):  # straight into the file image
+                        pieces += [(o + head + t, _PLAIN_MID), (o + ln - 1, b'}')]
+                        self._encode_data(text, fp + o + head + t + mid)
+                    else:
+                        pieces.append((o + head + t, _PLAIN_MID + text + b'}'))
+                return pieces
+
+            return self._emit(lens, order, file_digests, fill)
+
     def _run_encrypted(self, prepared, file_digests):
-        torch, L, over = self._torch, self.digest_size, self.overhead
+        L, over = self.digest_size, self.overhead
         n, nb, kb = len(prepared), self.cipher.nonce_bytes, self.cipher.key_bytes
         # device-given slots last; within each kind, the data hashed on the device first
         order = sorted(range(n), key=lambda i: (isinstance(prepared[i][0], DeviceDigests),
@@ -641,14 +545,13 @@ class GpuSnapshotWriter:
         on_host = [y >= self.host_digest_min for y in ylen]
         stream = self._stream.cuda_stream
         enc = self.encryption
-        with torch.cuda.stream(self._stream):
+        with self._torch.cuda.stream(self._stream):
             bases, firsts, counts = self._slots(prepared, order)
             tlen = [self.table_len(counts[i]) for i in order]
             xlen = [t + over for t in tlen]
             # upload: user key | nonces of data | nonces of tables (random ones) | serialize(data) texts
-            key_off, dn_off = 0, SLOT
-            tn_off = dn_off + _up(nb * n)
-            at = tn_off + _up(nb * n)
+            key_off = 0
+            (dn_off, tn_off), at = _offsets([nb * n, nb * n], SLOT)
             if self.nonces is None:
                 noise = os.urandom(2 * nb * n)
                 data_nonces, table_nonces = noise[:nb * n], noise[nb * n:]
@@ -661,43 +564,31 @@ class GpuSnapshotWriter:
                 pieces.append((dn_off, data_nonces))
             if table_nonces is not None:
                 pieces.append((tn_off, table_nonces))
-            t_off = []
-            for t in texts:
-                t_off.append(at)
-                if not isinstance(t, _DataPlan):
-                    pieces.append((at, t))
-                at += _up(_text_len(t))
-            d_up = self._pinned_to_device('up', pieces, at)
+            t_off, at = _offsets(map(_text_len, texts), at)
+            pieces += [(o, t) for o, t in zip(t_off, texts) if not isinstance(t, _DataPlan)]
+            d_up = self._upload('up', pieces, at)
             up = d_up.data_ptr()
             for k in planned:  # straight into the cipher's input
                 self._encode_data(texts[k], up + t_off[k])
             dn_ptr = up + dn_off
             if data_nonces is None:
-                size = sum(_up(texts[k].length) for k in planned)
-                h_dt = self._buf.get('h_dt', max(size, 16), pinned=True)
-                spans, a = {}, 0
-                for k in planned:
-                    ln = texts[k].length
+                ats, size = _offsets(texts[k].length for k in planned)
+                h_dt = self._buf.get('h_dt', max(size, ALIGN), pinned=True)
+                spans = {k: (a, texts[k].length) for k, a in zip(planned, ats)}
+                for k, (a, ln) in spans.items():
                     h_dt[a:a + ln].copy_(d_up[t_off[k]:t_off[k] + ln], non_blocking=True)
-                    spans[k] = (a, ln)
-                    a += _up(ln)
                 self.stats['bytes_copied_back'] += size
                 self._stream.synchronize()
                 dt = h_dt.numpy()
                 seen = [dt[spans[k][0]:spans[k][0] + spans[k][1]].tobytes() if k in spans else t
                         for k, t in enumerate(texts)]
                 data_nonces = b''.join(self._nonce(self.nonces(t, self.userkey)) for t in seen)
-                dn_ptr = self._pinned_to_device('dn', [(0, data_nonces)], nb * n).data_ptr()
+                dn_ptr = self._upload('dn', [(0, data_nonces)], nb * n).data_ptr()
             # blobs, table texts: 16-aligned offsets each
-            y_off, x_off, q = [], [], 0
-            for y in ylen:
-                y_off.append(q)
-                q += _up(y)
-            for x in xlen:
-                x_off.append(q)
-                q += _up(x)
-            d_blob = self._buf.get('d_blob', max(q, 16))
-            d_text = self._buf.get('d_text', max(q, 16))  # table i's text at its blob's offset
+            y_off, q = _offsets(ylen)
+            x_off, q = _offsets(xlen, q)
+            d_blob = self._buf.get('d_blob', max(q, ALIGN))
+            d_text = self._buf.get('d_text', max(q, ALIGN))  # table i's text at its blob's offset
             d_dd = self._buf.get('d_dd', n * SLOT)
             bp = d_blob.data_ptr()
             # 1. data under the user key
@@ -722,13 +613,11 @@ class GpuSnapshotWriter:
                 h_dd[:n * SLOT].copy_(d_dd[:n * SLOT], non_blocking=True)
                 self.stats['bytes_copied_back'] += n * SLOT
             if hosted:
-                size = sum(_up(ylen[k]) for k in hosted)
+                ats, size = _offsets(ylen[k] for k in hosted)
                 h_y = self._buf.get('h_y', size, pinned=True)
-                spans, a = [], 0
-                for k in hosted:
-                    h_y[a:a + ylen[k]].copy_(d_blob[y_off[k]:y_off[k] + ylen[k]], non_blocking=True)
-                    spans.append((a, ylen[k]))
-                    a += _up(ylen[k])
+                spans = [(a, ylen[k]) for k, a in zip(hosted, ats)]
+                for k, (a, ln) in zip(hosted, spans):
+                    h_y[a:a + ln].copy_(d_blob[y_off[k]:y_off[k] + ln], non_blocking=True)
                 self.stats['bytes_copied_back'] += size
             if h_dd is not None:
                 self._stream.synchronize()
@@ -750,7 +639,7 @@ class GpuSnapshotWriter:
                     subkey = hashlib.blake2b(dd[k, :L].tobytes(), salt=enc.shared_kdf_params, key=enc.shared_key,
                                              digest_size=kb).digest()
                     made.append(self._nonce(self.nonces(self._table_prefix(prepared[i][0], counts[i]), subkey)))
-                d_tn = self._pinned_to_device('tn', [(0, b''.join(made))], nb * n)
+                d_tn = self._upload('tn', [(0, b''.join(made))], nb * n)
                 tn_ptr = d_tn.data_ptr()
             else:
                 tn_ptr = up + tn_off
@@ -760,28 +649,20 @@ class GpuSnapshotWriter:
             # 4. the file image
             xb, yb = [b64_len(x) for x in xlen], [b64_len(y) for y in ylen]
             lens = [len(_ENC_HEAD) + a + len(_ENC_MID) + b + len(_ENC_TAIL) for a, b in zip(xb, yb)]
-            offs, total = [], 0
-            for ln in lens:
-                offs.append(total)
-                total += _up(ln)
-            d_file = self._buf.get('d_file', max(total, 16))
-            fp = d_file.data_ptr()
-            ins = _ptr_array([bp + o for o in x_off + y_off])
-            in_lens = _ptr_array(xlen + ylen)
-            outs = _ptr_array([fp + o + len(_ENC_HEAD) for o in offs] +
-                              [fp + o + len(_ENC_HEAD) + a + len(_ENC_MID) for o, a in zip(offs, xb)])
-            check(lib().rc_snapshot_b64_encode_device(self._h, 2 * n, ins.ctypes.data, in_lens.ctypes.data,
-                                                      outs.ctypes.data, stream))
-            pieces = []
-            for o, a, ln in zip(offs, xb, lens):
-                pieces += [(o, _ENC_HEAD), (o + len(_ENC_HEAD) + a, _ENC_MID), (o + ln - len(_ENC_TAIL), _ENC_TAIL)]
-            self._place(d_file, pieces)
-            small, h_fd = self._file_digests(d_file, offs, lens, file_digests)
-            contents, digests = self._finish(d_file, offs, lens, total, small, h_fd, file_digests)
-        back = [None] * n
-        for k, i in enumerate(order):
-            back[i] = (contents[k], digests[k])
-        return [b[0] for b in back], [b[1] for b in back]
+
+            def fill(fp, offs):
+                ins = _ptr_array([bp + o for o in x_off + y_off])
+                in_lens = _ptr_array(xlen + ylen)
+                outs = _ptr_array([fp + o + len(_ENC_HEAD) for o in offs] +
+                                  [fp + o + len(_ENC_HEAD) + a + len(_ENC_MID) for o, a in zip(offs, xb)])
+                check(lib().rc_snapshot_b64_encode_device(self._h, 2 * n, ins.ctypes.data, in_lens.ctypes.data,
+                                                          outs.ctypes.data, stream))
+                pieces = []
+                for o, a, ln in zip(offs, xb, lens):
+                    pieces += [(o, _ENC_HEAD), (o + len(_ENC_HEAD) + a, _ENC_MID), (o + ln - len(_ENC_TAIL), _ENC_TAIL)]
+                return pieces
+
+            return self._emit(lens, order, file_digests, fill)
 
     def _nonce(self, nonce) -> bytes:
         nonce = bytes(nonce)

@@ -60,13 +60,15 @@ from .cipher import DecryptionError
 from .hashing import SLOT, hasher_from_config, hashlib_from_config, state_init
 from .naming import ChunkNaming, parse_snapshot_location
 from .pipeline import ChunkEncryption, DeviceSnapshotProducer, hashing_arguments
-from .restore import DEFAULT_BATCH
+from .restore import ALIGN, DEFAULT_BATCH, _up
 
-ALIGN = 16
 NO_COUNT = (1 << 64) - 1  # rc_snapshot_table_count: no canonical table has that length
 
 _ENC_HEAD, _ENC_MID, _ENC_TAIL = b'{"chunks":{"!b":"', b'"},"data":{"!b":"', b'"}}'
-_PLAIN_HEAD, _PLAIN_MID = b'{"chunks":[', b',"data":'
+# an unencrypted file is _PLAIN_HEAD + table text + _PLAIN_MID + serialize(data) + b'}'; the table
+# text opens with its own bracket, so a file begins with _PLAIN_OPEN
+_PLAIN_HEAD, _PLAIN_MID = b'{"chunks":', b',"data":'
+_PLAIN_OPEN = _PLAIN_HEAD + b'['
 
 
 def type_reverse(obj):
@@ -115,9 +117,9 @@ def split_plain(contents) -> Optional[Tuple[int, int, int, int]]:
     """(t0, t1, d0, d1) if ``contents`` is ``{"chunks":[T],"data":D}`` where the first ``]`` ends
     the table: contents[t0:t1] is the table with its brackets, contents[d0:d1] is D, which the
     caller must still find to be one JSON value.  None for any other shape."""
-    if not (contents.startswith(_PLAIN_HEAD) and contents.endswith(b'}')):
+    if not (contents.startswith(_PLAIN_OPEN) and contents.endswith(b'}')):
         return None
-    t0 = len(_PLAIN_HEAD) - 1
+    t0 = len(_PLAIN_HEAD)
     k = contents.find(b']', t0)
     if k < 0 or contents[k + 1:k + 1 + len(_PLAIN_MID)] != _PLAIN_MID:
         return None
@@ -138,8 +140,14 @@ def _decoded_len(contents, a, b) -> Optional[int]:
     return n // 4 * 3 - (contents[b - 1] == 61) - (contents[b - 2] == 61)
 
 
-def _up(n):
-    return (n + ALIGN - 1) // ALIGN * ALIGN
+def _offsets(lens, at=0):
+    """(offs, end): where buffers of ``lens`` bytes start when they lie back to back from ``at``,
+    each at a multiple of ALIGN, and where the last one's room ends."""
+    offs = []
+    for ln in lens:
+        offs.append(at)
+        at += _up(ln)
+    return offs, at
 
 
 @dataclass
@@ -352,22 +360,21 @@ class _Buffers:
         return cur
 
 
-class GpuSnapshotLoader:
-    """Snapshot bodies of one repository, loaded on one HIP device.  ``encryption`` is the
-    repository's (None: unencrypted), ``userkey`` the key that decrypts ``data`` (None: ``data``
-    is never decrypted), ``hashing`` / ``digest_size`` / ``hash_bits`` its hashing adapter as
-    ``DeviceRestorer`` takes them.  ``host_digest_min`` overrides the length from which a ``data``
-    field is hashed on host threads."""
+class _SnapshotHandle:
+    """What ``GpuSnapshotLoader`` and ``GpuSnapshotWriter`` (snapshot_write.py) share: the
+    ``rc_snapshot`` handle of one repository on one HIP device with the hasher and the cipher it
+    borrows, the stream and the named buffers of its calls, the host threads that hash what is too
+    long for the device, and the timers.  A subclass says whether it hashes without a cipher too
+    (``_ALWAYS_HASHES``), how its threads are called and which ``stats`` it counts."""
+    _ALWAYS_HASHES = False
+    _THREAD_PREFIX = 'snapshot-digest'
+    _STATS: Tuple[str, ...] = ()
 
-    def __init__(self, *, encryption: Optional[ChunkEncryption], userkey: Optional[bytes] = None,
-                 hashing='blake2b', digest_size=None, hash_bits=None, batch_bytes=DEFAULT_BATCH,
-                 device=None, host_digest_min: Optional[int] = None):
+    def __init__(self, *, encryption: Optional[ChunkEncryption], userkey, hashing, digest_size, hash_bits, device,
+                 host_digest_min):
         digest_size, hash_bits, hash_args = hashing_arguments(hashing, digest_size, hash_bits)
         self.hashing, self.hash_bits, self.digest_size = hashing, hash_bits, digest_size
         self._hashlib_args = ({'length': digest_size} if hashing == 'blake2b' else {'bits': hash_bits})
-        if int(batch_bytes) < 1:
-            raise ValueError('batch_bytes must be positive')
-        self.batch_bytes = int(batch_bytes)
         self.encryption = encryption
         self.encrypted = encryption is not None
         self.userkey = None if userkey is None else bytes(userkey)
@@ -375,10 +382,12 @@ class GpuSnapshotLoader:
                                 if host_digest_min is None else int(host_digest_min))
         self._h = None
         self.device = int(_current_device() if device is None else device)
-        handle = ctypes.c_void_p()
-        if self.encrypted:
-            # the handles first: without a GPU this is where ChunkerUnavailable is raised
+        # the handles first: without a GPU this is where ChunkerUnavailable is raised
+        self.hasher = self.cipher = kdf = None
+        if self.encrypted or self._ALWAYS_HASHES:
             self.hasher = hasher_from_config(hashing, device=self.device, **hash_args)
+        code = RC_CIPHER_NONE
+        if self.encrypted:
             self.cipher = encryption.make_cipher(self.device)
             if self.userkey is not None and len(self.userkey) != self.cipher.key_bytes:
                 raise ValueError('Invalid key size')
@@ -386,12 +395,9 @@ class GpuSnapshotLoader:
                              salt=encryption.shared_kdf_params)
             code = (RC_CIPHER_CHACHA20_POLY1305 if encryption.cipher == 'chacha20_poly1305'
                     else RC_CIPHER_AES_GCM)
-            check(lib().rc_snapshot_create(digest_size, code, self.cipher.handle(), kdf, self.device,
-                                           ctypes.byref(handle)))
-        else:
-            self.hasher = self.cipher = None
-            check(lib().rc_snapshot_create(digest_size, RC_CIPHER_NONE, None, None, self.device,
-                                           ctypes.byref(handle)))
+        handle = ctypes.c_void_p()
+        check(lib().rc_snapshot_create(digest_size, code, self.cipher.handle() if self.cipher else None, kdf,
+                                       self.device, ctypes.byref(handle)))
         self._h = handle
         self.overhead = int(lib().rc_snapshot_overhead(handle))
         self.stride = int(lib().rc_snapshot_stride(handle))
@@ -401,8 +407,7 @@ class GpuSnapshotLoader:
         self._stream = torch.cuda.Stream(device=self.dev)
         self._buf = _Buffers(torch, self.dev)
         self._pool = None
-        self.stats = dict.fromkeys(('snapshots', 'host_fallbacks', 'data_digests_host', 'data_digests_device',
-                                    'bytes_uploaded', 'bytes_copied_back', 'data_bytes_copied_back'), 0)
+        self.stats = dict.fromkeys(self._STATS, 0)
 
     def close(self):
         """Release the native handles and the buffers (the object is unusable after)."""
@@ -431,19 +436,69 @@ class GpuSnapshotLoader:
         except Exception:
             pass
 
-    # ---------------------------------------------------------------------- profiling
+    def _live(self):
+        if not self._h:
+            raise RuntimeError(f'{type(self).__name__} is closed')
 
     def timing(self, enable: bool):
         check(lib().rc_snapshot_timing_enable(self._h, 1 if enable else 0))
 
+    def _read_timers(self, symbol, ms_names, calls_name) -> dict:
+        """One ``rc_snapshot_*timing_read``: its milliseconds under ``ms_names``, its call count."""
+        ms = [ctypes.c_double() for _ in ms_names]
+        calls = ctypes.c_uint64()
+        check(getattr(lib(), symbol)(self._h, *(ctypes.byref(m) for m in ms), ctypes.byref(calls)))
+        return {**{name: m.value for name, m in zip(ms_names, ms)}, calls_name: calls.value}
+
+    def _hash(self, data) -> bytes:
+        h = hashlib_from_config(self.hashing, **self._hashlib_args)
+        h.update(data)
+        return h.digest()
+
+    def _threads(self):
+        if self._pool is None:
+            self._pool = ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1),
+                                            thread_name_prefix=self._THREAD_PREFIX)
+        return self._pool
+
+    def _upload(self, name, pieces, total):
+        """pieces: (offset, uint8 array or bytes-like) into the pinned image ``h_<name>``, copied
+        to the device buffer ``d_<name>`` on the handle's stream.  Returns the device tensor."""
+        h = self._buf.get('h_' + name, max(total, ALIGN), pinned=True)
+        d = self._buf.get('d_' + name, max(total, ALIGN))
+        h_np = h.numpy()
+        for off, data in pieces:
+            view = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.reshape(-1)
+            h_np[off:off + view.size] = view
+        if total:
+            d[:total].copy_(h[:total], non_blocking=True)
+        self.stats['bytes_uploaded'] += total
+        return d
+
+
+class GpuSnapshotLoader(_SnapshotHandle):
+    """Snapshot bodies of one repository, loaded on one HIP device.  ``encryption`` is the
+    repository's (None: unencrypted), ``userkey`` the key that decrypts ``data`` (None: ``data``
+    is never decrypted), ``hashing`` / ``digest_size`` / ``hash_bits`` its hashing adapter as
+    ``DeviceRestorer`` takes them.  ``host_digest_min`` overrides the length from which a ``data``
+    field is hashed on host threads."""
+    _THREAD_PREFIX = 'snapshot-data-digest'
+    _STATS = ('snapshots', 'host_fallbacks', 'data_digests_host', 'data_digests_device', 'bytes_uploaded',
+              'bytes_copied_back', 'data_bytes_copied_back')
+
+    def __init__(self, *, encryption: Optional[ChunkEncryption], userkey: Optional[bytes] = None,
+                 hashing='blake2b', digest_size=None, hash_bits=None, batch_bytes=DEFAULT_BATCH,
+                 device=None, host_digest_min: Optional[int] = None):
+        if int(batch_bytes) < 1:
+            raise ValueError('batch_bytes must be positive')
+        self.batch_bytes = int(batch_bytes)
+        super().__init__(encryption=encryption, userkey=userkey, hashing=hashing, digest_size=digest_size,
+                         hash_bits=hash_bits, device=device, host_digest_min=host_digest_min)
+
     def timing_read(self) -> dict:
         """Summed kernel milliseconds since the last read: subkeys + decrypt + wipe, table
         decode, bulk base64."""
-        ms = [ctypes.c_double() for _ in range(3)]
-        calls = ctypes.c_uint64()
-        check(lib().rc_snapshot_timing_read(self._h, *(ctypes.byref(m) for m in ms), ctypes.byref(calls)))
-        return {'crypt_ms': ms[0].value, 'decode_ms': ms[1].value, 'b64_ms': ms[2].value,
-                'decode_calls': calls.value}
+        return self._read_timers('rc_snapshot_timing_read', ('crypt_ms', 'decode_ms', 'b64_ms'), 'decode_calls')
 
     # ------------------------------------------------------------------------ helpers
 
@@ -468,11 +523,6 @@ class GpuSnapshotLoader:
                 continue
             admitted.append(path)
         return admitted
-
-    def _hash(self, data) -> bytes:
-        h = hashlib_from_config(self.hashing, **self._hashlib_args)
-        h.update(data)
-        return h.digest()
 
     def reference_body(self, contents, want_data=True) -> dict:
         """``_decrypt_snapshot_body`` restated: json, base64 and hashlib on the host and the
@@ -526,8 +576,7 @@ class GpuSnapshotLoader:
         ``data`` the device does not accept (``accept_stripped``) is deserialised on the host as
         before, counts in ``stats['host_fallbacks']`` and gives the same object.
         The result is in the order of ``items``."""
-        if not self._h:
-            raise RuntimeError('GpuSnapshotLoader is closed')
+        self._live()
         items = [(path, bytes(contents)) for path, contents in items]
         out: List[Optional[LoadedSnapshot]] = [None] * len(items)
         split = split_encrypted if self.encrypted else split_plain
@@ -543,8 +592,7 @@ class GpuSnapshotLoader:
         for pos, (path, contents) in enumerate(items):
             spans = split(contents)
             if spans is None:
-                out[pos] = self._fallback(path, contents, want_chunks, want_data)
-                self._reference_host(out[pos], into, select)
+                self._load_on_host(out, pos, path, contents, into, select, want_chunks, want_data)
                 continue
             if batch and size + len(contents) > self.batch_bytes:
                 flush()
@@ -576,30 +624,27 @@ class GpuSnapshotLoader:
         for first, count in merged:
             into.reference_device(d_slots.data_ptr() + SLOT * first, count)
 
-    def _upload(self, pieces, total):
-        """pieces: (offset, bytes-like) into one pinned image, copied to the device on the
-        loader's stream.  Returns the device tensor."""
-        torch = self._torch
-        h = self._buf.get('h_up', max(total, ALIGN), pinned=True)
-        d = self._buf.get('d_up', max(total, ALIGN))
-        h_np = h.numpy()
-        for off, data in pieces:
-            view = np.frombuffer(data, dtype=np.uint8)
-            h_np[off:off + view.size] = view
-        if total:
-            d[:total].copy_(h[:total], non_blocking=True)
-        self.stats['bytes_uploaded'] += total
-        return d
+    def _load_on_host(self, out, pos, path, contents, into, select, want_chunks, want_data):
+        """Snapshot ``pos`` the reference's way, and its digests to the planner from the host."""
+        out[pos] = self._fallback(path, contents, want_chunks, want_data)
+        self._reference_host(out[pos], into, select)
+
+    def _slots_back(self, d_slots, slots, want_chunks) -> np.ndarray:
+        """Enqueue the copy of the first ``slots`` digest slots to pinned memory; returns their
+        (slots, 64) view, which holds them after the synchronisation (empty when not wanted)."""
+        if not (want_chunks and slots):
+            return np.empty((0, SLOT), dtype=np.uint8)
+        h_slots = self._buf.get('h_slots', slots * SLOT, pinned=True)
+        h_slots[:slots * SLOT].copy_(d_slots[:slots * SLOT], non_blocking=True)
+        self.stats['bytes_copied_back'] += slots * SLOT
+        return h_slots.numpy()[:slots * SLOT].reshape(slots, SLOT)
 
     # -------------------------------------------------------------------- parts of `data`
 
     def read_timing_read(self) -> dict:
         """Summed kernel milliseconds of the four stages that read ``data`` since the last read."""
-        ms = [ctypes.c_double() for _ in range(4)]
-        calls = ctypes.c_uint64()
-        check(lib().rc_snapshot_read_timing_read(self._h, *(ctypes.byref(m) for m in ms), ctypes.byref(calls)))
-        return {'find_ms': ms[0].value, 'parse_ms': ms[1].value, 'sums_ms': ms[2].value, 'strip_ms': ms[3].value,
-                'find_calls': calls.value}
+        return self._read_timers('rc_snapshot_read_timing_read', ('find_ms', 'parse_ms', 'sums_ms', 'strip_ms'),
+                                 'find_calls')
 
     def _parts_begin(self, ptrs, lens, full=False):
         """Enqueue the four stages over the device texts ``ptrs[i]`` of ``lens[i]`` bytes on the
@@ -609,10 +654,7 @@ class GpuSnapshotLoader:
         job = SimpleNamespace(n=len(lens), lens=[int(x) for x in lens], full=full)
         n = job.n
         cap = job.cap = sum(parts_room(ln) for ln in job.lens)
-        job.out_off, total = [], 0
-        for ln in job.lens:
-            job.out_off.append(total)
-            total += _up(ln)
+        job.out_off, total = _offsets(job.lens)
 
         def room(name, nbytes):
             t = self._buf.get('p_' + name, max(nbytes, ALIGN))
@@ -753,8 +795,7 @@ class GpuSnapshotLoader:
         """Read the parts of n texts that lie in device memory (``ptrs[i]``, ``lens[i]`` bytes, any
         alignment), in one call: what ``load(parts=True)`` runs on every ``data``, for tests and
         probes."""
-        if not self._h:
-            raise RuntimeError('GpuSnapshotLoader is closed')
+        self._live()
         if not len(lens):
             return []
         with self._torch.cuda.stream(self._stream):
@@ -831,32 +872,27 @@ class GpuSnapshotLoader:
                 datas[b] = deserialize(contents[d0:d1])
                 keep.append(b)
             except ValueError:
-                out[pos] = self._fallback(path, contents, want_chunks, want_data)
-                self._reference_host(out[pos], into, select)
+                self._load_on_host(out, pos, path, contents, into, select, want_chunks, want_data)
         n = len(keep)
         if not n:
             return
         k_of = [None] * len(batch)
-        offs, lens, pieces, total = [], [], [], 0
         for k, b in enumerate(keep):
             k_of[b] = k
-            _, _, contents, (t0, t1, _, _) = batch[b]
-            offs.append(total)
-            lens.append(t1 - t0)
-            pieces.append((total, memoryview(contents)[t0:t1]))
-            total += _up(t1 - t0)
+        # the upload image: the table text of every item, then with parts every D
+        kept = [(batch[b][2], batch[b][3]) for b in keep]
+        lens = [t1 - t0 for _, (t0, t1, _, _) in kept]
+        offs, total = _offsets(lens)
+        pieces = [(o, memoryview(contents)[t0:t1]) for o, (contents, (t0, t1, _, _)) in zip(offs, kept)]
         d_offs = []
         if parts:
-            for b in keep:
-                _, _, contents, (_, _, d0, d1) = batch[b]
-                d_offs.append(total)
-                pieces.append((total, memoryview(contents)[d0:d1]))
-                total += _up(d1 - d0)
+            d_offs, total = _offsets([d1 - d0 for _, (_, _, d0, d1) in kept], total)
+            pieces += [(o, memoryview(contents)[d0:d1]) for o, (contents, (_, _, d0, d1)) in zip(d_offs, kept)]
         counts = np.zeros(n, dtype=np.uint64)
         want = [self.table_count(ln) or 0 for ln in lens]
         slots = sum(want)
         with torch.cuda.stream(self._stream):
-            d_up = self._upload(pieces, total)
+            d_up = self._upload('up', pieces, total)
             d_slots = self._buf.get('d_slots', max(slots, 1) * SLOT)
             d_status = self._buf.get('d_status', n)
             h_status = self._buf.get('h_status', n, pinned=True)
@@ -870,16 +906,9 @@ class GpuSnapshotLoader:
                 job = self._parts_begin([d_up.data_ptr() + o for o in d_offs],
                                         [batch[b][3][3] - batch[b][3][2] for b in keep])
             h_status[:n].copy_(d_status[:n], non_blocking=True)
-            slots_np = None
-            if want_chunks and slots:
-                h_slots = self._buf.get('h_slots', slots * SLOT, pinned=True)
-                h_slots[:slots * SLOT].copy_(d_slots[:slots * SLOT], non_blocking=True)
-                slots_np = h_slots.numpy()[:slots * SLOT].reshape(slots, SLOT)
-                self.stats['bytes_copied_back'] += slots * SLOT
+            slots_np = self._slots_back(d_slots, slots, want_chunks)
             self._stream.synchronize()
         self.stats['bytes_copied_back'] += n
-        if slots_np is None:
-            slots_np = np.empty((0, SLOT), dtype=np.uint8)
         firsts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.uint64)
         if job is not None:
             for k, tp in enumerate(self._parts_finish(job)):
@@ -890,8 +919,7 @@ class GpuSnapshotLoader:
                     try:
                         datas[b] = self._data_on_host(contents[d0:d1])
                     except ValueError:
-                        out[pos] = self._fallback(path, contents, want_chunks, want_data)
-                        self._reference_host(out[pos], into, select)
+                        self._load_on_host(out, pos, path, contents, into, select, want_chunks, want_data)
                         k_of[b] = None
 
         def plain_of(k):  # the text is on the host already
@@ -914,8 +942,7 @@ class GpuSnapshotLoader:
                 except binascii.Error:
                     ylen = None
             if xlen is None or ylen is None:  # a field that is not canonical base64
-                out[pos] = self._fallback(path, contents, want_chunks, want_data)
-                self._reference_host(out[pos], into, select)
+                self._load_on_host(out, pos, path, contents, into, select, want_chunks, want_data)
             elif ydec is not None:
                 host_items.append((b, xlen, ylen, ydec))
             else:
@@ -924,10 +951,7 @@ class GpuSnapshotLoader:
         n, m = len(order), len(dev_items)
         if not n:
             return
-        if host_items and self._pool is None:
-            self._pool = ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1),
-                                            thread_name_prefix='snapshot-data-digest')
-        futures = [self._pool.submit(self._hash, it[3]) for it in host_items]
+        futures = [self._threads().submit(self._hash, it[3]) for it in host_items]
         self.stats['data_digests_host'] += len(host_items)
         self.stats['data_digests_device'] += m
         k_of = [None] * len(batch)
@@ -959,16 +983,13 @@ class GpuSnapshotLoader:
                 dec += _up(ylen)
         plain_lens = [max(it[1] - over, 0) for it in order]
         data_lens = [max(it[2] - over, 0) for it in order]
-        q_off, q = [], 0
-        for ln in data_lens:
-            q_off.append(q)
-            q += _up(ln)
+        q_off, q = _offsets(data_lens)
         want = [self.table_count(ln) or 0 for ln in plain_lens]
         slots = sum(want)
         counts = np.zeros(n, dtype=np.uint64)
         stream = self._stream.cuda_stream
         with torch.cuda.stream(self._stream):
-            d_up = self._upload(pieces, up)
+            d_up = self._upload('up', pieces, up)
             d_dec = self._buf.get('d_dec', max(dec, ALIGN))
             d_plain = self._buf.get('d_plain', max(dec, ALIGN))  # table i's plaintext at its blob's offset
             d_slots = self._buf.get('d_slots', max(slots, 1) * SLOT)
@@ -1027,16 +1048,9 @@ class GpuSnapshotLoader:
                     self.stats['bytes_copied_back'] += q
                     self.stats['data_bytes_copied_back'] += q
             h_flags[:3 * n + m].copy_(d_flags[:3 * n + m], non_blocking=True)
-            slots_np = None
-            if want_chunks and slots:
-                h_slots = self._buf.get('h_slots', slots * SLOT, pinned=True)
-                h_slots[:slots * SLOT].copy_(d_slots[:slots * SLOT], non_blocking=True)
-                slots_np = h_slots.numpy()[:slots * SLOT].reshape(slots, SLOT)
-                self.stats['bytes_copied_back'] += slots * SLOT
+            slots_np = self._slots_back(d_slots, slots, want_chunks)
             self._stream.synchronize()
         self.stats['bytes_copied_back'] += 3 * n + m
-        if slots_np is None:
-            slots_np = np.empty((0, SLOT), dtype=np.uint8)
         flags = h_flags.numpy()
         status, ok_x, ok_y = flags[:n], flags[n:2 * n], flags[2 * n:2 * n + m]
         ok_data = flags[2 * n + m:3 * n + m]
@@ -1046,8 +1060,7 @@ class GpuSnapshotLoader:
         for k, (b, xlen, ylen, ydec) in enumerate(order):
             if not ok_x[k] or (k < m and not ok_y[k]):
                 pos, path, contents, _ = batch[b]
-                out[pos] = self._fallback(path, contents, want_chunks, want_data)
-                self._reference_host(out[pos], into, select)
+                self._load_on_host(out, pos, path, contents, into, select, want_chunks, want_data)
                 k_of[b] = None
 
         def plain_of(k):  # tag verified, text not canonical: the reference deserialises it

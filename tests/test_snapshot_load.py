@@ -150,6 +150,22 @@ def test_plain_split_never_disagrees_with_json_on_what_it_accepts():
         assert json.loads(table) == parsed['chunks'] and data == parsed['data']
 
 
+def test_the_writer_and_the_split_share_one_plain_envelope():
+    from replicat_amd import snapshot_write, snapshots
+    assert snapshot_write._PLAIN_HEAD is snapshots._PLAIN_HEAD and snapshot_write._PLAIN_MID is snapshots._PLAIN_MID
+    contents = snapshot_write.assemble_plain(b'[{"!b":"QQ=="}]', b'{"a":1}')
+    assert contents == b'{"chunks":[{"!b":"QQ=="}],"data":{"a":1}}'
+    t0, t1, d0, d1 = split_plain(contents)
+    assert (contents[t0:t1], contents[d0:d1]) == (b'[{"!b":"QQ=="}]', b'{"a":1}')
+
+
+def test_offsets_lay_buffers_back_to_back_at_multiples_of_16():
+    from replicat_amd.snapshots import _offsets
+    assert _offsets([]) == ([], 0) and _offsets([], 48) == ([], 48)
+    assert _offsets([0, 1, 16, 17, 0]) == ([0, 0, 16, 32, 64], 64)
+    assert _offsets((n for n in (5, 40)), 64) == ([64, 80], 128)  # any iterable, from a given start
+
+
 # ------------------------------------------------------------------ the length rule
 
 def count_for(width, plain_len):
@@ -216,6 +232,16 @@ def test_sources_and_symbols_are_registered():
     for name in re.findall(r'\b(rc_snapshot_\w+)\(', header):
         assert name in _lib.SIGNATURES, name
     assert 'rc_gc_reference_device(' in open(os.path.join(build.ROOT, 'include', 'replicat_gc.h')).read()
+
+
+def test_the_headers_the_snapshot_files_include_take_part_in_the_build_id():
+    import re
+    hashed = {os.path.basename(p) for p in build.HEADERS}
+    sources = [p for p in build.SOURCES + build.HEADERS if 'snapshot' in os.path.basename(p)]
+    assert len(sources) >= 8
+    for path in sources:
+        for name in re.findall(r'#include "(?:\.\./)*(?:include/)?(\w+\.h)"', open(path).read()):
+            assert name in hashed, (os.path.basename(path), name)
 
 
 # ------------------------------------------------------------------ locations
