@@ -254,6 +254,71 @@ int rc_snapshot_data_timing_read(rc_snapshot *s, double *parts_ms, double *scan_
                                  uint64_t *encode_calls);
 
 /* ---------------------------------------------------------------------------------------------
+ * Writing the files' text: the m + 1 fixed pieces of "Writing `data`" made on the device as well,
+ * from columns, instead of being uploaded packed.  `order` lists the files: listed file j is file
+ * d_order[j] of the columns.
+ *     head(j) = {"path": Q ,"chunks":[           tail(j) = ,"digest": D [,"metadata": M]
+ *     piece 0 = first + head(0)
+ *     piece j = tail(j - 1) + }, + head(j)       0 < j < m
+ *     piece m = tail(m - 1) + }] + last          (with m == 0 the one piece is first + last)
+ * `first` ({"utc_timestamp":"..","files":[) and `last` ([,"note":".."]}) are the caller's bytes.
+ * Q is the path as json's encode_basestring_ascii writes it, read from the bytes of
+ * str.encode('utf-8', 'surrogatepass'): \" \\ \b \t \n \f \r, \u00xx for the other bytes below
+ * 0x20 and for 0x7f, \uxxxx (lowercase) for every two- and three-byte sequence -- lone surrogates
+ * included -- and a surrogate pair for every four-byte one.  D is null for a file flagged
+ * unfinished, else {"!b":"<base64 of the first digest_size bytes of its 64-byte slot>"}.  M, present
+ * when d_metadata is, is null for an unfinished file, else
+ *     {"st_mode":a,"st_uid":b,"st_gid":c,"st_size":d,"st_atime_ns":e,"st_mtime_ns":f,"st_ctime_ns":g}
+ * with the file's RC_SNAPSHOT_METADATA_COLUMNS values as signed 64-bit decimals.
+ *
+ * Columns (all DEVICE memory, indexed by file, not by place in the listing): d_path_bytes with
+ * d_path_off (m + 1 words of 64 bits, not decreasing: path f is the bytes d_path_off[f] ..
+ * d_path_off[f + 1] - 1); d_digests (64-byte slots, 16-byte aligned); d_unfinished (one byte per
+ * file, or NULL: none is); d_metadata (m rows of seven int64, or NULL: no metadata key).  The
+ * caller hands in what str.encode wrote, so the device rejects nothing: a lead byte's read of its
+ * continuation bytes is clamped to the path's end, offsets to d_path_off[m] and d_order to m - 1;
+ * input outside the rules gives text that means nothing, and no access outside the arrays.
+ * Both calls are enqueued on hip_stream without a synchronisation.  RC_ERR_ARGUMENT: a NULL handle
+ * or array, m of 2^32 or more, digest_size outside 1..64.  Kernels: replicat_amd/csrc/
+ * snapshot_text.hip.
+ * ------------------------------------------------------------------------------------------- */
+
+#define RC_SNAPSHOT_METADATA_COLUMNS 7
+
+/* Host only: the bytes of Q for a path of `len` bytes of generalised UTF-8: 2 and, per byte, 1
+ * (0x20..0x7e but " and \), 2 (" \ and the five short escapes), 6 (other control bytes, 0x7f,
+ * and the lead bytes 0xc0..0xef), 12 (lead bytes from 0xf0) or 0 (continuation bytes). */
+uint64_t rc_snapshot_path_text_len_for(const uint8_t *utf8, uint64_t len);
+
+/* Host only: the characters of `value` as a decimal with a '-' where it is negative: 1 to 20. */
+uint32_t rc_snapshot_int64_len_for(int64_t value);
+
+/* The length pass, between stages 1 and 2 of "Writing `data`": d_piece_len[j], j <= m, is the
+ * length of piece j -- what stage 2 scans (m + 2 words; the last is stage 2's). */
+int rc_snapshot_file_text_len_device(rc_snapshot *s, uint64_t m, const uint32_t *d_order,
+                                     const uint8_t *d_path_bytes, const uint64_t *d_path_off,
+                                     uint32_t digest_size, const uint8_t *d_digests,
+                                     const uint8_t *d_unfinished, const int64_t *d_metadata,
+                                     uint64_t first_len, uint64_t last_len, uint64_t *d_piece_len,
+                                     void *hip_stream);
+
+/* The text pass, after stage 2: piece j at d_text + d_piece_off[j] (d_text at any alignment),
+ * exactly its bytes -- those of the parts between the pieces, like those before and after the
+ * text, are not touched.  Stage 3 is then called with d_pieces NULL and the same d_text. */
+int rc_snapshot_encode_file_text_device(rc_snapshot *s, uint64_t m, const uint32_t *d_order,
+                                        const uint8_t *d_path_bytes, const uint64_t *d_path_off,
+                                        uint32_t digest_size, const uint8_t *d_digests,
+                                        const uint8_t *d_unfinished, const int64_t *d_metadata,
+                                        const uint8_t *d_first, uint64_t first_len, const uint8_t *d_last,
+                                        uint64_t last_len, const uint64_t *d_piece_off, uint8_t *d_text,
+                                        void *hip_stream);
+
+/* The two passes in the kernel timing rc_snapshot_timing_enable switches on: the summed
+ * milliseconds of the length passes (len_ms) and of the text passes (text_ms, and their number
+ * in calls); clears them. */
+int rc_snapshot_file_text_timing_read(rc_snapshot *s, double *len_ms, double *text_ms, uint64_t *calls);
+
+/* ---------------------------------------------------------------------------------------------
  * Reading `data`: the way back, from the text of serialize(data) to the parts as arrays, for a
  * batch of n texts per call (one call serves many small snapshots).  serialize escapes every quote
  * inside a JSON string, so the ten bytes {"range":[ occur in the text only where a part starts and

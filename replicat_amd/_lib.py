@@ -203,6 +203,13 @@ SIGNATURES = {
     'rc_snapshot_encode_data_device': (_int, [_p, _u64, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
     'rc_snapshot_data_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
+    'rc_snapshot_path_text_len_for': (_u64, [_p, _u64]),
+    'rc_snapshot_int64_len_for': (_u32, [ctypes.c_int64]),
+    'rc_snapshot_file_text_len_device': (_int, [_p, _u64, _p, _p, _p, _u32, _p, _p, _p, _u64, _u64, _p, _p]),
+    'rc_snapshot_encode_file_text_device': (_int, [_p, _u64, _p, _p, _p, _u32, _p, _p, _p, _p, _u64, _p, _u64, _p, _p,
+                                                   _p]),
+    'rc_snapshot_file_text_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                 ctypes.POINTER(_u64)]),
     'rc_snapshot_parts_room': (_u64, [_u64]),
     'rc_snapshot_find_parts_device': (_int, [_p, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
     'rc_snapshot_parse_parts_device': (_int, [_p, _u64, _p, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),

@@ -25,11 +25,12 @@ static_assert(RC_TABLE_OK == RC_CHUNK_OK && RC_TABLE_BAD_TAG == RC_CHUNK_BAD_TAG
 
 namespace {
 
-// The event pairs of a handle, one per stage (the four rc_snapshot_*timing_read).
+// The event pairs of a handle, one per stage (the five rc_snapshot_*timing_read).
 enum Timer {
     kCrypt, kDecode, kB64,         // loading (snapshot.hip)
     kEncode, kB64Encode, kSeal,    // writing (snapshot_write.hip)
     kParts, kScan, kData,          // writing `data` (snapshot_data.hip)
+    kTextLen, kText,               // writing the files' text (snapshot_text.hip)
     kFind, kParse, kSums, kStrip,  // reading `data` (snapshot_parse.hip)
     kTimers
 };
@@ -287,7 +288,7 @@ int bulk_locked(rc_snapshot *s, const std::vector<SnapText> &texts, uint64_t per
     return s->ring.finish(*g.w, st);
 }
 
-// Behind the four *timing_read: the timers in the order given.
+// Behind the five *timing_read: the timers in the order given.
 struct TimerOut {
     Timer t;
     double *ms;
@@ -674,6 +675,74 @@ int rc_snapshot_encode_data_device(rc_snapshot *s, uint64_t n, uint64_t m, const
 int rc_snapshot_data_timing_read(rc_snapshot *s, double *parts_ms, double *scan_ms, double *encode_ms,
                                  uint64_t *encode_calls) {
     return read_timers(s, {{kParts, parts_ms, nullptr}, {kScan, scan_ms, nullptr}, {kData, encode_ms, encode_calls}});
+}
+
+// ----------------------------------------------------------------------- writing the files' text
+
+uint64_t rc_snapshot_path_text_len_for(const uint8_t *utf8, uint64_t len) {
+    uint64_t sum = 2;
+    for (uint64_t k = 0; k < len; ++k) sum += rc_snap_path_term(utf8[k]);
+    return sum;
+}
+
+uint32_t rc_snapshot_int64_len_for(int64_t value) { return rc_snap_int64_len(value); }
+
+namespace {
+
+// What both passes check before a device is touched, and the columns as the kernels take them.
+int check_file_text(const rc_snapshot *s, uint64_t m, const uint32_t *d_order, const uint8_t *d_path_bytes,
+                    const uint64_t *d_path_off, uint32_t digest_size, const uint8_t *d_digests,
+                    const uint8_t *d_unfinished, const int64_t *d_metadata, uint64_t first_len, uint64_t last_len,
+                    SnapFileText &a) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    if (m > 0xFFFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "2^32 or more files");
+    if (digest_size < 1 || digest_size > RC_DIGEST_SLOT)
+        return rc_fail(RC_ERR_ARGUMENT, "digest_size must be 1..64, not %u", digest_size);
+    if (m && (!d_order || !d_path_bytes || !d_path_off || !d_digests)) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    if (reinterpret_cast<uintptr_t>(d_digests) & 15) return rc_fail(RC_ERR_ALIGN, "d_digests is not 16-byte aligned");
+    a = SnapFileText{m, d_order, d_path_bytes, d_path_off, digest_size, d_digests, d_unfinished, d_metadata,
+                     first_len, last_len};
+    return 0;
+}
+
+}  // namespace
+
+int rc_snapshot_file_text_len_device(rc_snapshot *s, uint64_t m, const uint32_t *d_order, const uint8_t *d_path_bytes,
+                                     const uint64_t *d_path_off, uint32_t digest_size, const uint8_t *d_digests,
+                                     const uint8_t *d_unfinished, const int64_t *d_metadata, uint64_t first_len,
+                                     uint64_t last_len, uint64_t *d_piece_len, void *hip_stream) {
+    SnapFileText a;
+    if (int rc = check_file_text(s, m, d_order, d_path_bytes, d_path_off, digest_size, d_digests, d_unfinished,
+                                 d_metadata, first_len, last_len, a))
+        return rc;
+    if (!d_piece_len) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    return rc::timed(s->timers[kTextLen], st, [&] { return rc_snap_launch_file_text_len(a, d_piece_len, st); });
+}
+
+int rc_snapshot_encode_file_text_device(rc_snapshot *s, uint64_t m, const uint32_t *d_order,
+                                        const uint8_t *d_path_bytes, const uint64_t *d_path_off, uint32_t digest_size,
+                                        const uint8_t *d_digests, const uint8_t *d_unfinished,
+                                        const int64_t *d_metadata, const uint8_t *d_first, uint64_t first_len,
+                                        const uint8_t *d_last, uint64_t last_len, const uint64_t *d_piece_off,
+                                        uint8_t *d_text, void *hip_stream) {
+    SnapFileText a;
+    if (int rc = check_file_text(s, m, d_order, d_path_bytes, d_path_off, digest_size, d_digests, d_unfinished,
+                                 d_metadata, first_len, last_len, a))
+        return rc;
+    if (!d_piece_off || !d_text || (first_len && !d_first) || (last_len && !d_last))
+        return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    return rc::timed(s->timers[kText], st,
+                     [&] { return rc_snap_launch_file_text(a, d_first, d_last, d_piece_off, d_text, st); });
+}
+
+int rc_snapshot_file_text_timing_read(rc_snapshot *s, double *len_ms, double *text_ms, uint64_t *calls) {
+    return read_timers(s, {{kTextLen, len_ms, nullptr}, {kText, text_ms, calls}});
 }
 
 // ------------------------------------------------------------------------------- reading `data`

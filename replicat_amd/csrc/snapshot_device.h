@@ -1,7 +1,8 @@
-// snapshot_device.h -- what the four snapshot .hip files share (snapshot.hip, snapshot_write.hip,
-// snapshot_data.hip, snapshot_parse.hip): the global address space and its granule types, the
-// staging of a span through LDS, the workgroup scan, the one binary search, and the launchers'
-// grid size.  Device helpers are always inlined: a file that uses none of them compiles as before.
+// snapshot_device.h -- what the five snapshot .hip files share (snapshot.hip, snapshot_write.hip,
+// snapshot_data.hip, snapshot_text.hip, snapshot_parse.hip): the global address space and its
+// granule types, the staging of a span through LDS, the base64 characters, the workgroup scan, the
+// one binary search, and the launchers' grid size.  Device helpers are always inlined: a file that
+// uses none of them compiles as before.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,6 +23,25 @@ __device__ __forceinline__ uint32_t stage_span(uint8_t *lds, gcbytes p, uint32_t
     const uint32_t granules = (skew + len + 15) >> 4;
     for (uint32_t k = threadIdx.x; k < granules; k += kSnapThreads) dst[k] = src[k];
     return skew;
+}
+
+// The character of a 6-bit value (standard alphabet): A-Z a-z 0-9 + /
+__device__ __forceinline__ uint32_t b64_char(uint32_t v) {
+    uint32_t c = v + 'A';
+    c += v >= 26 ? uint32_t('a' - 'Z' - 1) : 0u;
+    c -= v >= 52 ? uint32_t('z' + 1 - '0') : 0u;
+    c -= v >= 62 ? uint32_t('9' + 1 - '+') : 0u;
+    c += v >= 63 ? uint32_t('/' - '+' - 1) : 0u;
+    return c;
+}
+
+// Three bytes (the first on top of 24 bits) as four characters, the first in the low byte; the
+// last `pad` of them are '='.
+__device__ __forceinline__ uint32_t b64_quad(uint32_t t, uint32_t pad) {
+    const uint32_t c0 = b64_char(t >> 18), c1 = b64_char((t >> 12) & 63u);
+    const uint32_t c2 = pad >= 2 ? uint32_t('=') : b64_char((t >> 6) & 63u);
+    const uint32_t c3 = pad >= 1 ? uint32_t('=') : b64_char(t & 63u);
+    return c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
 }
 
 // Exclusive prefix of v over the workgroup's lanes, and the sum; lds holds kSnapThreads words.

@@ -13,7 +13,7 @@ constexpr uint64_t kSnapReject = ~uint64_t(0);  // a count / length the host alr
 
 // 4 * ceil(L / 3): the base64 characters of an L-byte digest; a record is 10 bytes longer
 // ({"!b":" and "} and the separator after it).
-inline uint32_t rc_snap_chars(uint32_t digest_bytes) { return 4 * ((digest_bytes + 2) / 3); }
+__host__ __device__ inline uint32_t rc_snap_chars(uint32_t digest_bytes) { return 4 * ((digest_bytes + 2) / 3); }
 inline uint32_t rc_snap_stride(uint32_t digest_bytes) { return rc_snap_chars(digest_bytes) + 10; }
 
 // One plaintext table: `count` records (kSnapReject: no canonical table has this length) whose
@@ -105,6 +105,51 @@ int rc_snap_launch_encode_data(const uint32_t *d_records, const uint64_t *d_part
 // The `count` packed pieces at their offsets in d_text.
 int rc_snap_launch_place_pieces(const uint8_t *d_pieces, const uint64_t *d_piece_pre, const uint64_t *d_piece_off,
                                 uint64_t count, uint8_t *d_text, hipStream_t st);
+
+// snapshot_text.hip: the m + 1 fixed pieces of serialize(data), from columns.  One wave per piece:
+// kSnapTextWaves pieces per workgroup; a path is read kSnapTextStep bytes per wave step.
+constexpr uint32_t kSnapTextWaves = kSnapThreads / 64;
+constexpr uint32_t kSnapTextStep = 64;
+constexpr uint32_t kSnapMetaColumns = RC_SNAPSHOT_METADATA_COLUMNS;
+constexpr uint32_t kSnapMetaFixed = 88;  // {"st_mode":,"st_uid":, ... "st_ctime_ns":} without the seven numbers
+
+// What one byte of a path's generalised UTF-8 adds to the length of its JSON string
+// (encode_basestring_ascii): the byte alone decides.
+__host__ __device__ inline uint32_t rc_snap_path_term(uint32_t b) {
+    if (b >= 0xF0u) return 12;  // a surrogate pair
+    if (b >= 0xC0u) return 6;   // \uxxxx
+    if (b >= 0x80u) return 0;   // a continuation byte: its lead byte's
+    if (b == '"' || b == '\\') return 2;
+    if (b >= 0x20u) return b == 0x7Fu ? 6 : 1;
+    return b == '\b' || b == '\t' || b == '\n' || b == '\f' || b == '\r' ? 2 : 6;
+}
+
+// The characters of v as a signed decimal: 1 to 20.
+__host__ __device__ inline uint32_t rc_snap_int64_len(int64_t v) {
+    const uint64_t u = v < 0 ? uint64_t(0) - uint64_t(v) : uint64_t(v);
+    uint32_t nd = 1;
+    for (uint64_t p = 10; nd < 20 && u >= p; p *= 10) ++nd;  // 10^19 < 2^64: p does not wrap while nd < 20
+    return nd + (v < 0 ? 1u : 0u);
+}
+
+// The columns both passes read (include/replicat_snapshot.h, "Writing the files' text").
+struct SnapFileText {
+    uint64_t m;
+    const uint32_t *order;
+    const uint8_t *path_bytes;
+    const uint64_t *path_off;
+    uint32_t digest_bytes;
+    const uint8_t *digests;
+    const uint8_t *unfinished;  // or null
+    const int64_t *metadata;    // or null: no metadata key
+    uint64_t first_len, last_len;
+};
+
+// d_piece_len[j], j <= m: the bytes of fixed piece j.
+int rc_snap_launch_file_text_len(const SnapFileText &a, uint64_t *d_piece_len, hipStream_t st);
+// Piece j at d_text + d_piece_off[j], and no other byte.
+int rc_snap_launch_file_text(const SnapFileText &a, const uint8_t *d_first, const uint8_t *d_last,
+                             const uint64_t *d_piece_off, uint8_t *d_text, hipStream_t st);
 
 // snapshot_parse.hip: the parts read back from the text of `data`.  A part is then
 // RC_SNAPSHOT_PART_WORDS words: run (the ordinal of its list among the lists of the call), start,

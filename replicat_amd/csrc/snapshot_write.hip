@@ -38,25 +38,6 @@ constexpr uint32_t kBulkInLds = kBulkIn + 32;                                // 
 constexpr uint32_t kBulkChars = kSnapThreads * kSnapLaneChars;
 constexpr uint32_t kBulkCharsLds = kBulkChars + 16;
 
-// The character of a 6-bit value (standard alphabet): A-Z a-z 0-9 + /
-__device__ __forceinline__ uint32_t b64_char(uint32_t v) {
-    uint32_t c = v + 'A';
-    c += v >= 26 ? uint32_t('a' - 'Z' - 1) : 0u;
-    c -= v >= 52 ? uint32_t('z' + 1 - '0') : 0u;
-    c -= v >= 62 ? uint32_t('9' + 1 - '+') : 0u;
-    c += v >= 63 ? uint32_t('/' - '+' - 1) : 0u;
-    return c;
-}
-
-// Three bytes (the first on top of 24 bits) as four characters, the first in the low byte; the
-// last `pad` of them are '='.
-__device__ __forceinline__ uint32_t b64_quad(uint32_t t, uint32_t pad) {
-    const uint32_t c0 = b64_char(t >> 18), c1 = b64_char((t >> 12) & 63u);
-    const uint32_t c2 = pad >= 2 ? uint32_t('=') : b64_char((t >> 6) & 63u);
-    const uint32_t c3 = pad >= 1 ? uint32_t('=') : b64_char(t & 63u);
-    return c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
-}
-
 // Puts the first `len` bytes of w (word k = bytes 4k .. 4k + 3; len <= 4 N) at lds + off, off any
 // byte: aligned words where all four bytes are this record's, single bytes elsewhere, so that
 // lanes with adjacent records never write each other's bytes.

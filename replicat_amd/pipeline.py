@@ -247,18 +247,27 @@ class SnapshotStream:
                 d['digest'] = f.digest
         return out
 
-    def layout(self):
+    def layout(self, columns=False):
         """The same run as arrays (``snapshot_write.SnapshotLayout``): the cuts, the table indices
         and the bounds, paths and digests of the files, with no object per part -- what
-        ``GpuSnapshotWriter`` takes, inside a ``SnapshotData``, in place of ``snapshot_files()``."""
+        ``GpuSnapshotWriter`` takes, inside a ``SnapshotData``, in place of ``snapshot_files()``.
+        With ``columns`` the digests are an ``(m, L)`` array, with ``unfinished`` set where a file
+        has none: the columnar form, whose per-file text the device writes as well."""
         from .snapshot_write import SnapshotLayout  # imports this module
         n, m = len(self.chunks), len(self.files)
-        return SnapshotLayout(
+        lay = SnapshotLayout(
             chunk_ends=np.fromiter((c.stream_end for c in self.chunks), dtype=np.uint64, count=n),
             table_index=np.fromiter((c.table_index for c in self.chunks), dtype=np.uint32, count=n),
             file_starts=np.fromiter((f.stream_start for f in self.files), dtype=np.uint64, count=m),
             file_ends=np.fromiter((f.stream_end for f in self.files), dtype=np.uint64, count=m),
             paths=[f.path for f in self.files], digests=[f.digest for f in self.files])
+        if columns:
+            width = max((len(d) for d in lay.digests if d is not None), default=1)
+            unfinished = np.fromiter((d is None for d in lay.digests), dtype=np.bool_, count=m)
+            lay.digests = np.frombuffer(b''.join(bytes(width) if d is None else d for d in lay.digests),
+                                        dtype=np.uint8).reshape(m, width)
+            lay.unfinished = unfinished if unfinished.any() else None
+        return lay
 
 
 def _fstat_size(record, src):

@@ -12,7 +12,8 @@ What it replaces, in replicat's repository.py: ``_encrypt_snapshot_body`` (:982-
 
 ``GpuSnapshotWriter.write`` serialises a ``data`` dict -- irregular JSON -- on the host (or, given
 a ``SnapshotData``, writes the part records of its files on the device between per-file text the
-host supplies: include/replicat_snapshot.h, "Writing `data`"), encrypts it under
+host supplies -- or, for a columnar layout, the device writes from the files' columns as well:
+include/replicat_snapshot.h, "Writing `data`" and "Writing the files' text"), encrypts it under
 the user key on the device, hashes the result there (or, when it is long, on host threads:
 ``DeviceSnapshotProducer.HOST_DIGEST_MIN_BY_HASH``, the loader's rule), encodes the table text from
 the 64-byte digest slots, derives the subkey and seals the table (``rc_snapshot_seal_tables_device``),
@@ -46,6 +47,11 @@ from .snapshots import (ALIGN, _ENC_HEAD, _ENC_MID, _ENC_TAIL, _PLAIN_HEAD, _PLA
 
 NONCE_PREFIX = 64   # bytes of a table's text an injected nonce rule is shown
 SMALL_PIECE = 4096  # fixed parts shorter than this are placed by one scatter
+# the columns of a metadata array: read_metadata's keys, in its order (repository.py:505-519)
+METADATA_KEYS = ('st_mode', 'st_uid', 'st_gid', 'st_size', 'st_atime_ns', 'st_mtime_ns', 'st_ctime_ns')
+# the text kernel's geometry (csrc/snapshot_kernels.h): fixed pieces per workgroup, path bytes per wave step
+FILE_TEXT_PIECES_PER_GROUP = 4
+FILE_TEXT_STEP = 64
 
 
 def assemble_encrypted(chunks_blob, data_blob) -> bytes:
@@ -70,7 +76,13 @@ class SnapshotLayout:
     ``chunk_ends[k]`` (it starts where chunk k - 1 ends, chunk 0 at 0) and refers to slot
     ``table_index[k]`` of the table; file f is the bytes ``file_starts[f] .. file_ends[f]``, has
     ``paths[f]``, ``digests[f]`` (bytes or None) and, when ``metadata`` is given, ``metadata[f]``.
-    ``SnapshotStream.layout()`` builds one from a producer's records."""
+    ``SnapshotStream.layout()`` builds one from a producer's records.
+
+    The COLUMNAR form keeps the files' fields as arrays, and the device then writes their text as
+    well: ``digests`` an ``(m, L)`` uint8 array (L in 1..64), ``metadata`` None or an ``(m, 7)``
+    int64 array whose columns are ``METADATA_KEYS``, and ``unfinished``, a bool array of length m,
+    true for a file whose digest and metadata are null (one flag for both, as _chunk_done sets
+    them together: repository.py:1403-1406).  ``paths`` stays a sequence of ``str``."""
     chunk_ends: Any
     table_index: Any
     file_starts: Any
@@ -78,6 +90,7 @@ class SnapshotLayout:
     paths: Sequence[str]
     digests: Sequence[Optional[bytes]]
     metadata: Optional[Sequence[Any]] = None
+    unfinished: Optional[Any] = None
 
     def __post_init__(self):
         self.chunk_ends = _array(self.chunk_ends, np.uint64, 'chunk_ends')
@@ -93,6 +106,42 @@ class SnapshotLayout:
     def m(self) -> int:
         return int(self.file_starts.size)
 
+    @property
+    def columnar(self) -> bool:
+        """Whether the device can write the files' text: the digests are an array and the
+        metadata, if any, is one."""
+        return isinstance(self.digests, np.ndarray) and (self.metadata is None or isinstance(self.metadata, np.ndarray))
+
+    def _validate_columns(self):
+        m, d, meta, unf = self.m, self.digests, self.metadata, self.unfinished
+        if isinstance(d, np.ndarray):
+            if d.dtype != np.uint8 or d.ndim != 2:
+                raise ValueError(f'digests must be an (m, L) uint8 array, not {d.dtype} {d.shape}')
+            if not 1 <= d.shape[1] <= SLOT:
+                raise ValueError(f'digests of {d.shape[1]} bytes: the width must be 1..{SLOT}')
+        if isinstance(meta, np.ndarray):
+            if meta.dtype != np.int64 or meta.ndim != 2 or meta.shape[1] != len(METADATA_KEYS):
+                raise ValueError(f'metadata must be an (m, {len(METADATA_KEYS)}) int64 array, not {meta.dtype} '
+                                 f'{meta.shape}')
+        if unf is not None:
+            if not isinstance(d, np.ndarray):
+                raise ValueError('unfinished belongs to digests given as an array; a list marks them with None')
+            unf = np.asarray(unf)
+            if unf.dtype != np.bool_ or unf.shape != (m,):
+                raise ValueError(f'unfinished must be a bool array of length {m}, not {unf.dtype} {unf.shape}')
+            self.unfinished = unf
+
+    def file_objects(self):
+        """(digests, metadata) as the lists of objects of a layout that is not columnar: rows as
+        ``bytes``, metadata rows as ``read_metadata``'s dicts, None for an unfinished file."""
+        digests, meta, unf = self.digests, self.metadata, self.unfinished
+        done = [True] * self.m if unf is None else (~unf).tolist()
+        if isinstance(digests, np.ndarray):
+            digests = [row.tobytes() if ok else None for row, ok in zip(digests, done)]
+        if isinstance(meta, np.ndarray):
+            meta = [dict(zip(METADATA_KEYS, row)) if ok else None for row, ok in zip(meta.tolist(), done)]
+        return digests, meta
+
     def validate(self, counter0: int = 1):
         """ValueError unless the arrays are what the device stages take for granted
         (include/replicat_snapshot.h, "Writing `data`"): nothing is left for the device to reject."""
@@ -104,6 +153,7 @@ class SnapshotLayout:
             raise ValueError('file_starts, file_ends, paths and digests differ in length')
         if self.metadata is not None and len(self.metadata) != m:
             raise ValueError('metadata and paths differ in length')
+        self._validate_columns()
         if not 0 <= int(counter0) < 1 << 32 or n >= 1 << 32 or m >= 1 << 32 or (n and int(counter0) + n - 1 >= 1 << 32):
             raise ValueError('the number of chunks, of files and the last counter must be below 2^32')
         if n:
@@ -151,16 +201,36 @@ class SnapshotData:
     utc_timestamp: str
     note: Optional[str] = None
     counter0: int = 1
+    file_text: Optional[str] = None  # 'host' | 'device'; None: 'device' for a columnar layout
+
+    def text_mode(self) -> str:
+        """Where the fixed text of the files is written: 'device' takes a columnar layout."""
+        mode = self.file_text
+        if mode is None:
+            return 'device' if self.layout.columnar else 'host'
+        if mode not in ('host', 'device'):
+            raise ValueError(f"file_text must be 'host', 'device' or None, not {mode!r}")
+        if mode == 'device' and not self.layout.columnar:
+            raise ValueError("file_text='device' needs a columnar layout: digests as an (m, L) uint8 array and "
+                             'metadata as None or an (m, 7) int64 array')
+        return mode
+
+    def ends(self) -> Tuple[str, str]:
+        """The text before the first file's entry and behind the ']' of ``files``."""
+        quote = json.encoder.encode_basestring_ascii
+        return ('{"utc_timestamp":' + quote(self.utc_timestamp) + ',"files":[',
+                (',"note":' + quote(self.note) if self.note is not None else '') + '}')
 
     def pieces(self, order) -> List[str]:
         """The text of ``serialize(data)`` around the part records of the files ``order`` lists:
-        len(order) + 1 pieces; the parts of listed file j go between pieces j and j + 1."""
+        len(order) + 1 pieces; the parts of listed file j go between pieces j and j + 1.  The
+        host twin of csrc/snapshot_text.hip: a columnar layout is turned into objects first."""
         lay, quote = self.layout, json.encoder.encode_basestring_ascii
-        first = '{"utc_timestamp":' + quote(self.utc_timestamp) + ',"files":['
-        last = (',"note":' + quote(self.note) if self.note is not None else '') + '}'
+        first, last = self.ends()
         if len(order) == 0:
             return [first + ']' + last]
-        paths, digests, meta = lay.paths, lay.digests, lay.metadata
+        paths = lay.paths
+        digests, meta = lay.file_objects()
         b64 = base64.standard_b64encode
         heads = ['{"path":' + quote(paths[f]) + ',"chunks":[' for f in order]
         tails = [',"digest":' + ('null' if digests[f] is None else '{"!b":"' + str(b64(digests[f]), 'ascii') + '"}')
@@ -202,7 +272,7 @@ class GpuSnapshotWriter(_SnapshotHandle):
     _ALWAYS_HASHES = True  # the file's own digest
     _THREAD_PREFIX = 'snapshot-write-digest'
     _STATS = ('snapshots', 'bytes_uploaded', 'bytes_copied_back', 'data_digests_host', 'data_digests_device',
-              'file_digests_host', 'file_digests_device', 'data_syncs')
+              'file_digests_host', 'file_digests_device', 'data_syncs', 'device_file_texts')
 
     def __init__(self, *, encryption: Optional[ChunkEncryption], userkey: Optional[bytes] = None,
                  hashing='blake2b', digest_size=None, hash_bits=None, device=None,
@@ -225,6 +295,10 @@ class GpuSnapshotWriter(_SnapshotHandle):
         scans and offsets, text."""
         return self._read_timers('rc_snapshot_data_timing_read', ('parts_ms', 'scan_ms', 'data_encode_ms'),
                                  'data_encode_calls')
+
+    def file_text_timing_read(self) -> dict:
+        """Summed kernel milliseconds of the two passes over the files' text since the last read."""
+        return self._read_timers('rc_snapshot_file_text_timing_read', ('text_len_ms', 'text_ms'), 'text_calls')
 
     # ------------------------------------------------------------------------ helpers
 
@@ -271,6 +345,7 @@ class GpuSnapshotWriter(_SnapshotHandle):
         for _, data in items:  # refused before anything is enqueued
             if isinstance(data, SnapshotData):
                 data.layout.validate(data.counter0)
+                data.text_mode()
         prepared = [(self._rows(chunks), data if isinstance(data, SnapshotData) else serialize(data))
                     for chunks, data in items]
         if not prepared:
@@ -320,12 +395,38 @@ class GpuSnapshotWriter(_SnapshotHandle):
 
     def _stage_lengths(self, p, pieces):
         """Stage 2: the fixed pieces go up packed with their lengths; the total comes back."""
-        torch = self._torch
         lens = np.zeros(p.m + 2, dtype=np.uint64)
         lens[:p.m + 1] = np.fromiter(map(len, pieces), dtype=np.uint64, count=p.m + 1)
         packed = np.frombuffer(bytearray(''.join(pieces), 'ascii'), dtype=np.uint8)
         p.piece_pre = self._to_device(lens)
         p.pieces = self._to_device(packed)
+        self._scan_lengths(p)
+
+    def _stage_file_text(self, p, data, order):
+        """The length pass over the columns of a columnar layout, then stage 2: no piece exists on
+        the host.  `p.columns` is what both passes read."""
+        torch, lay, m = self._torch, data.layout, p.m
+        packed, offsets = _pack_paths(lay.paths)
+        slots = np.zeros((m, SLOT), dtype=np.uint8)
+        slots[:, :lay.digests.shape[1]] = lay.digests
+        first, last = (np.frombuffer(bytearray(t, 'ascii'), dtype=np.uint8) for t in data.ends())
+        c = p.columns = _Columns()
+        c.digest_size = int(lay.digests.shape[1])
+        c.order = self._to_device(np.ascontiguousarray(order, dtype=np.uint32))
+        c.path_bytes = self._to_device(packed if packed.size else np.zeros(1, dtype=np.uint8))
+        c.path_off = self._to_device(offsets)
+        c.digests = self._to_device(slots.reshape(-1))
+        c.unfinished = None if lay.unfinished is None else self._to_device(lay.unfinished.astype(np.uint8))
+        c.metadata = None if lay.metadata is None else self._to_device(np.ascontiguousarray(lay.metadata).reshape(-1))
+        c.first, c.last = self._to_device(first), self._to_device(last)
+        p.piece_pre = torch.empty(m + 2, dtype=torch.int64, device=self.dev)
+        p.pieces = None
+        check(lib().rc_snapshot_file_text_len_device(self._h, m, *c.arguments(), c.first.numel(), c.last.numel(),
+                                                     p.piece_pre.data_ptr(), self._stream.cuda_stream))
+        self._scan_lengths(p)
+
+    def _scan_lengths(self, p):
+        torch = self._torch
         p.piece_off = torch.empty(p.m + 1, dtype=torch.int64, device=self.dev)
         p.total = torch.empty(1, dtype=torch.int64, device=self.dev)
         p.h_total = torch.empty(1, dtype=torch.int64).pin_memory()
@@ -335,12 +436,23 @@ class GpuSnapshotWriter(_SnapshotHandle):
         p.h_total.copy_(p.total, non_blocking=True)
         self.stats['bytes_copied_back'] += 8
 
+    def _encode_file_text(self, p, ptr):
+        """The text pass: the fixed pieces of plan `p`, from its columns, at device address `ptr`."""
+        c = p.columns
+        check(lib().rc_snapshot_encode_file_text_device(self._h, p.m, *c.arguments(), c.first.data_ptr(),
+                                                        c.first.numel(), c.last.data_ptr(), c.last.numel(),
+                                                        p.piece_off.data_ptr(), ptr, self._stream.cuda_stream))
+
     def _encode_data(self, p, ptr, with_pieces=True):
-        """Stage 3: the text of plan `p` at device address `ptr`."""
+        """Stage 3: the text of plan `p` at device address `ptr`; the fixed pieces of a plan with
+        columns come from the text pass, not from a packed buffer."""
+        if with_pieces and p.columns is not None:
+            self._encode_file_text(p, ptr)
+            self.stats['device_file_texts'] += 1
         check(lib().rc_snapshot_encode_data_device(self._h, p.n, p.m, p.part_first.data_ptr(), p.records.data_ptr(),
                                                    p.group.data_ptr(), p.piece_pre.data_ptr(), p.piece_off.data_ptr(),
-                                                   p.pieces.data_ptr() if with_pieces else None, ptr,
-                                                   self._stream.cuda_stream))
+                                                   p.pieces.data_ptr() if with_pieces and p.pieces is not None else None,
+                                                   ptr, self._stream.cuda_stream))
 
     def _plan_all(self, prepared):
         """Stages 1 and 2 of every ``SnapshotData`` among the items, then the one synchronisation
@@ -352,12 +464,14 @@ class GpuSnapshotWriter(_SnapshotHandle):
                 if not isinstance(data, SnapshotData):
                     continue
                 order = data.layout.listing()
-                pieces = data.pieces(order)
                 if len(order) == 0:
-                    prepared[k] = (rows, pieces[0].encode('ascii'))
+                    prepared[k] = (rows, data.pieces(order)[0].encode('ascii'))
                     continue
                 plan = self._stage_parts(data.layout, order, data.counter0)
-                self._stage_lengths(plan, pieces)
+                if data.text_mode() == 'device':
+                    self._stage_file_text(plan, data, order)
+                else:
+                    self._stage_lengths(plan, data.pieces(order))
                 prepared[k] = (rows, plan)
                 plans.append(plan)
             if plans:
@@ -689,9 +803,38 @@ class GpuSnapshotWriter(_SnapshotHandle):
 
 
 class _DataPlan:
-    """One ``SnapshotData`` after stages 1 and 2: the device arrays stage 3 reads, and ``length``,
-    the bytes of its text."""
+    """One ``SnapshotData`` after stages 1 and 2: the device arrays stage 3 reads, ``length``, the
+    bytes of its text, and ``columns`` when the device writes the fixed pieces as well."""
     length = 0
+    columns = None
+
+
+class _Columns:
+    """The files' fields on the device, as both passes over the files' text take them."""
+
+    def arguments(self):
+        return (self.order.data_ptr(), self.path_bytes.data_ptr(), self.path_off.data_ptr(), self.digest_size,
+                self.digests.data_ptr(), None if self.unfinished is None else self.unfinished.data_ptr(),
+                None if self.metadata is None else self.metadata.data_ptr())
+
+
+def _pack_paths(paths):
+    """The paths as one buffer of generalised UTF-8 (lone surrogates as three bytes) and their
+    m + 1 offsets, with one ``encode`` for all: the separators give the offsets.  A path that
+    holds U+0000 itself is legal; the lengths are then taken per path."""
+    m = len(paths)
+    joined = np.frombuffer(bytearray('\0'.join(paths).encode('utf-8', 'surrogatepass')), dtype=np.uint8)
+    cuts = np.flatnonzero(joined == 0)
+    offsets = np.zeros(m + 1, dtype=np.uint64)
+    if cuts.size == max(m - 1, 0):
+        packed = joined[joined != 0] if cuts.size else joined
+        offsets[1:m] = cuts - np.arange(m - 1)
+        offsets[m:] = packed.size
+    else:
+        packed = np.frombuffer(bytearray(''.join(paths).encode('utf-8', 'surrogatepass')), dtype=np.uint8)
+        lens = np.fromiter((len(p.encode('utf-8', 'surrogatepass')) for p in paths), dtype=np.uint64, count=m)
+        offsets[1:] = np.cumsum(lens)
+    return np.ascontiguousarray(packed), offsets
 
 
 def _text_len(text) -> int:
@@ -709,5 +852,6 @@ def _device_view(torch, ptr, nbytes, dev):
     return torch.as_tensor(_Span(ptr, nbytes), device=dev)
 
 
-__all__ = ['GpuSnapshotWriter', 'WrittenSnapshot', 'DeviceDigests', 'SnapshotLayout', 'SnapshotData', 'serialize', 'type_hint', 'assemble_encrypted',
+__all__ = ['GpuSnapshotWriter', 'WrittenSnapshot', 'DeviceDigests', 'SnapshotLayout', 'SnapshotData', 'METADATA_KEYS',
+           'serialize', 'type_hint', 'assemble_encrypted',
            'assemble_plain', 'b64_len', 'ChunkEncryption']
