@@ -58,7 +58,11 @@ extern "C" {
                       chain kernels on the reserved ones, so that this call's chain runs beside
                       the NEXT call's tile kernel.  The tile kernel waits for the work queued on
                       hip_stream before the call (the inputs); hip_stream does not wait for the
-                      outputs -- rc_chunk_wait does.  Same cuts as without the flag.  The
+                      outputs -- rc_chunk_wait does.  Same cuts as without the flag.  On the
+                      large-window path (max_length of about 1 MB or more) such a call's chain
+                      stream also runs tile launches: each stream's last max_length or so is
+                      read there in RC_TAIL_ROUNDS rounds, only as far as the stream's chain
+                      gets (rc_lazy_tail_split; not with RC_PIPELINE_END or RC_OPEN).  The
                       chunker's streams are blocking streams (HIP creates CU-masked streams so):
                       a caller on the legacy NULL stream gets correct but serial calls, so
                       pipelined callers use a non-blocking stream.  Calls the overlap does not
@@ -245,6 +249,19 @@ uint64_t rc_tile_keys(void);
  * receives the count, at most cap are written. */
 int rc_tile_schedule(uint64_t n_tiles, uint32_t waves, uint32_t permille, uint32_t chunk,
                      uint32_t dyn_min, uint32_t *ranges, uint64_t cap, uint64_t *n_units);
+
+/* Host-only inspection of the lazy-tail plan (tests; no device needed).  A pipelined call on
+ * the large-window path (max_length of about 1 MB or more) whose streams are one chain segment
+ * each reads a stream (L, P) in two parts: *body_tiles tiles of rc_tile_keys() keys on the tile
+ * stream -- through the tile holding the key of the last chunk start at which an argmax can
+ * happen, S* = max(P - max, L - 2 max) -- and the other *tiles - *body_tiles, up to
+ * rc_keys_needed, in RC_TAIL_ROUNDS rounds on the chain stream, each round only as far as the
+ * stream's chain has come.  Both are 0 for a stream the tail rule alone cuts. */
+int rc_lazy_tail_split(uint64_t max_length, uint64_t L, uint64_t P, uint64_t *tiles,
+                       uint64_t *body_tiles);
+/* Inspection (tests): waits for the chunker's last rc_chunk_device call; *rounds = the tail
+ * rounds it ran (0: not a lazy call), scanned[r] = the tiles round r read (at most cap). */
+int rc_chunker_tail_scanned(rc_chunker *ch, uint32_t *rounds, uint64_t *scanned, uint64_t cap);
 
 /* Host-only check of the table construction (no device needed): out[i] = key of data word
  * ds[i] under the 16-byte key, evaluated from the same byte tables the kernels use, and

@@ -158,6 +158,7 @@ struct rc_chunker {
         hipEvent_t done = nullptr;  // the call that last used this workspace has finished
         bool pending = false;
         bool piped = false;  // that call's chain ran on a pipelined stream, not the caller's
+        uint32_t lazy_rounds = 0;  // that call's tail rounds (0: not a lazy call)
     } ws[2];
     unsigned next_ws = 0;
 
@@ -203,6 +204,10 @@ struct Plan {
     uint64_t seg_bytes = 0, seg_cap = 0;
     bool any_multi = false;
     size_t bytes = 0;
+    bool lazy = false;    // lazy tails: the descriptor buffer holds the lazy block
+    uint64_t n_tail = 0;  // tail tiles of the call
+    uint64_t xt_tail_off = 0, lz_off = 0;  // the tail's list of tiles that are not fast and the
+                                           // lazy block, in u64 words of the descriptor buffer
 };
 
 // Layout of the descriptor buffer: ptr[n] len[n] last[n] jneed[n] tile_base[n+1] cut_base[n]
@@ -275,34 +280,12 @@ Workspace &acquire_ws(rc_chunker *ch) {
 
 int stage_descriptors(rc_chunker *ch, Workspace &ws, uint64_t n, const uint8_t *const *ptrs,
                       const uint64_t *lens, const uint64_t *last, Plan &plan, bool open = false,
-                      bool single = false, uint64_t walkers = 0) {
+                      bool single = false, uint64_t walkers = 0, bool lazy_ok = false) {
     plan.n = n;
     if (ws.pending) {  // the call that used this workspace before must be done with it
         RC_HIP_TRY(hipEventSynchronize(ws.done));
         ws.pending = false;
     }
-    // tiles the fast path does not take (kernels.hip tile_fast): a stream's tile 0 when the
-    // stream is shorter than a tile, and its last tile when the stream ends inside it
-    std::vector<uint64_t> &xt = ws.xtiles;
-    xt.clear();
-    {
-        uint64_t tiles = 0;
-        for (uint64_t i = 0; i < n; ++i) {
-            const uint64_t L = lens[i], P = open ? L : (last ? last[i] : 0);
-            const uint64_t jneed = rc_keys_needed(ch->max_length, L, P);
-            const uint64_t nt = jneed ? jneed / kTileKeys + 1 : 0;
-            const uint64_t jmax = L >= 8 ? (L - 4) / 4 : 0;
-            auto fast = [&](uint64_t t) { return L >= 8 && t * kTileKeys + kTileKeys - 1 <= jmax; };
-            if (nt && !fast(0)) xt.push_back(tiles);
-            if (nt > 1 && !fast(nt - 1)) xt.push_back(tiles + nt - 1);  // the tiles between are fast
-            tiles += nt;
-        }
-    }
-    plan.bytes = (9 * n + 3 + xt.size()) * sizeof(uint64_t);
-    if (int rc = ws.h_desc.ensure(plan.bytes)) return rc;
-    uint64_t *u = static_cast<uint64_t *>(ws.h_desc.p);
-    u[9 * n + 2] = xt.size();
-    std::copy(xt.begin(), xt.end(), u + 9 * n + 3);
     // Chain segments.  The chain of a stream is one wave walking ~(bound / chunk) steps; split
     // a stream only when the batch has too few streams to keep ~kChainWalkers waves busy, and
     // never below seg_floor (2) * max_length per segment (speculative chains meet within a few
@@ -332,7 +315,65 @@ int stage_descriptors(rc_chunker *ch, Workspace &ws, uint64_t n, const uint8_t *
         plan.seg_bytes = seg;
         plan.seg_cap = seg / step + ch->ext_steps + 4;
     }
-    uint64_t tiles = 0, cuts = 0, segs = 0, scratch = 0;
+    // Lazy tails (upload_and_launch): when the caller allows it and every stream
+    // is one chain segment, each stream's tiles split into a body, which the tile stream reads,
+    // and a tail, which the chain stream reads in rounds, only as far as the chain gets.
+    // The rounds have to fit beside the next call's body launch.  A tail is about one max_length
+    // per stream whatever its length, and it comes through the reserved CUs at ~0.55 TB/s
+    // (config 2: 3.4 GB and the rounds' launches in a 6.3 ms span) against the body's ~6.45
+    // TB/s (58.2 GB in 9.03 ms): the chain stream's span is ~7.8 x (tail tiles / body tiles) of
+    // the body launch's time, 0.70 for config 2's 312 / 3,472.  A call is lazy only while that
+    // stays under ~0.8: tail tiles at most RC_TAIL_SHARE per mille (100) of the body tiles.
+    // Shorter streams (L below ~12 max) read every tile in the one launch, as before.
+    plan.lazy = lazy_ok;
+    uint64_t all_tail = 0, all_body = 0;
+    for (uint64_t i = 0; i < n && plan.lazy; ++i) {
+        uint64_t b = 0, nt = 0, nb = 0;
+        const uint64_t P = open ? lens[i] : (last ? last[i] : 0);
+        if (!single && argmax_bound(ch->max_length, lens[i], P, b) && b / plan.seg_bytes != 0)
+            plan.lazy = false;
+        rc_lazy_tail_split(ch->max_length, lens[i], P, &nt, &nb);
+        all_tail += nt - nb;
+        all_body += nb;
+    }
+    if (all_tail * 1000 > all_body * (uint64_t)ch->knobs[knTailShare]) plan.lazy = false;
+    // tiles the fast path does not take (kernels.hip tile_fast): a stream's tile 0 when the
+    // stream is shorter than a tile, and its last tile when the stream ends inside it (lazy
+    // calls: the tail's in a list of their own)
+    std::vector<uint64_t> &xt = ws.xtiles;
+    std::vector<uint64_t> xt_tail;
+    xt.clear();
+    {
+        uint64_t tiles = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint64_t L = lens[i], P = open ? L : (last ? last[i] : 0);
+            uint64_t nt = 0, nb = 0;
+            rc_lazy_tail_split(ch->max_length, L, P, &nt, &nb);
+            if (!plan.lazy) nb = nt;
+            const uint64_t jmax = L >= 8 ? (L - 4) / 4 : 0;
+            auto fast = [&](uint64_t t) { return L >= 8 && t * kTileKeys + kTileKeys - 1 <= jmax; };
+            auto list = [&](uint64_t t) { (t < nb ? xt : xt_tail).push_back(tiles + t); };
+            if (nt && !fast(0)) list(0);
+            if (nt > 1 && !fast(nt - 1)) list(nt - 1);  // the tiles between are fast
+            tiles += nt;
+        }
+    }
+    // the lazy block after the lists: the tail's list, tail_base[n + 1], body[n], rec_off[n],
+    // the body launch's lengths[n], then the state have[n] want[n] pos[n] ncut[n]
+    plan.xt_tail_off = 9 * n + 3 + xt.size();
+    plan.lz_off = plan.xt_tail_off + 1 + xt_tail.size();
+    plan.bytes = (plan.lazy ? plan.lz_off + 8 * n + 1 : plan.xt_tail_off) * sizeof(uint64_t);
+    if (int rc = ws.h_desc.ensure(plan.bytes)) return rc;
+    uint64_t *u = static_cast<uint64_t *>(ws.h_desc.p);
+    u[9 * n + 2] = xt.size();
+    std::copy(xt.begin(), xt.end(), u + 9 * n + 3);
+    uint64_t *lz = nullptr;  // tail_base
+    if (plan.lazy) {
+        u[plan.xt_tail_off] = xt_tail.size();
+        std::copy(xt_tail.begin(), xt_tail.end(), u + plan.xt_tail_off + 1);
+        lz = u + plan.lz_off;
+    }
+    uint64_t tiles = 0, cuts = 0, segs = 0, scratch = 0, tail = 0;
     plan.any_multi = false;
     for (uint64_t i = 0; i < n; ++i) {
         const uint64_t L = lens[i], P = open ? L : (last ? last[i] : 0);
@@ -352,14 +393,30 @@ int stage_descriptors(rc_chunker *ch, Workspace &ws, uint64_t n, const uint8_t *
         u[2 * n + i] = P;
         u[3 * n + i] = jneed;
         u[4 * n + i] = tiles;
+        if (plan.lazy) {
+            uint64_t nt = 0, nb = 0;
+            rc_lazy_tail_split(ch->max_length, L, P, &nt, &nb);
+            lz[i] = tail;
+            lz[n + 1 + i] = nb;
+            lz[2 * n + 1 + i] = tiles + nb - tail;  // record index - tail launch index
+            // the body launch runs the ordinary kernel over the call's tiles with these lengths:
+            // exactly the stream's first nb tiles are fast (TileCursor::enter)
+            lz[3 * n + 1 + i] = std::min(L, nb * kTileKeys * 4);
+            lz[4 * n + 1 + i] = lz[5 * n + 1 + i] = nb * kTileKeys;  // have = want: the body
+            lz[6 * n + 1 + i] = lz[7 * n + 1 + i] = 0;               // pos, ncut
+            tail += nt - nb;
+        }
         tiles += jneed ? jneed / kTileKeys + 1 : 0;
         const uint64_t cap = cut_cap_of(ch->min_length, L);
         u[5 * n + 1 + i] = cuts;
-        u[6 * n + 1 + i] = cap;
+        const uint64_t cap_max = (uint64_t)ch->knobs[knCutCapMax];  // test switch
+        u[6 * n + 1 + i] = cap_max ? std::min(cap, cap_max) : cap;
         cuts += cap;
     }
     u[5 * n] = tiles;
     u[8 * n + 1] = segs;
+    if (plan.lazy) lz[n] = tail;
+    plan.n_tail = tail;
     // tile indices are 32-bit in the tile kernel's units and tie lists (kernels.hip TileUnits):
     // 2^32 tiles = 64 TiB of stream per call
     if (tiles >= (1ull << 32) - (1ull << 20))
@@ -381,9 +438,14 @@ uint32_t *tie_lists(Workspace &ws, const Plan &plan) {
     return reinterpret_cast<uint32_t *>(group_records(ws, plan) + plan.n_tiles + 1);
 }
 
+// a lazy call's tail rounds have tie lists of their own, after the body launch's
+uint32_t *tail_tie_lists(Workspace &ws, const Plan &plan) {
+    return tie_lists(ws, plan) + rc_tie_list_words(plan.n_tiles);
+}
+
 size_t records_bytes(const Plan &plan) {
     return (plan.n_tiles + 1) * (sizeof(TileRecord) + sizeof(GroupRecord)) +
-           rc_tie_list_words(plan.n_tiles) * 4;
+           (rc_tie_list_words(plan.n_tiles) + (plan.lazy ? rc_tie_list_words(plan.n_tail) : 0)) * 4;
 }
 
 // the grab counter: allocated and zeroed once per workspace; every edge kernel leaves it 0.  A
@@ -492,6 +554,26 @@ int upload_and_launch(rc_chunker *ch, Workspace &ws, const Plan &plan, ChainPara
     prm.fault = reinterpret_cast<const uint64_t *>(static_cast<uint32_t *>(ws.d_ctr.p) + kCtrStampWord);
     prm.epoch = ++ws.epoch;
     const StreamDesc d = desc_view(ws.d_desc.p, plan.n);
+    // Lazy tails: the tile stream reads each stream's body only -- the ordinary launch over
+    // the call's tiles, with lengths under which exactly the body tiles are fast -- and the
+    // chain stream reads the tails in rounds (below).
+    StreamDesc d_body = d, d_tail = d, d_tedge = d;
+    TileWindow win{};
+    const uint32_t rounds = plan.lazy && plan.n_tail ? (uint32_t)ch->knobs[knTailRounds] : 0u;
+    uint32_t *scanned = static_cast<uint32_t *>(ws.d_ctr.p) + kCtrScannedWord;
+    if (plan.lazy) {
+        uint64_t *lz = static_cast<uint64_t *>(ws.d_desc.p) + plan.lz_off;  // tail_base
+        const uint64_t n = plan.n;
+        d_tail.tile_base = lz;
+        d_tedge.xtiles = static_cast<uint64_t *>(ws.d_desc.p) + plan.xt_tail_off;
+        d_body.len = lz + 3 * n + 1;
+        prm.lz = LazyState{lz + 4 * n + 1, lz + 5 * n + 1, lz + 6 * n + 1, lz + 7 * n + 1};
+        win.have = prm.lz.have;
+        win.want = prm.lz.want;
+        win.body = lz + n + 1;
+        win.rec_off = lz + 2 * n + 1;
+        win.spare = plan.n_tiles;
+    }
     std::array<hipEvent_t, 4> ev{};
     if (ch->timing) {
         // round 5: timing events with the default system-scope fence cost a harness step
@@ -522,7 +604,7 @@ int upload_and_launch(rc_chunker *ch, Workspace &ws, const Plan &plan, ChainPara
     // 32-bit chain steps: small windows (the one-row record cache) and key indices < 2^32
     prm.lean = ch->small && plan.max_len < (16ull << 30) ? 1u : 0u;
     prm.hot = group_hot_threshold(ch->window);
-    if (int rc = rc_launch_tiles(ch->d_tables, d, plan.n, plan.n_tiles,
+    if (int rc = rc_launch_tiles(ch->d_tables, plan.lazy ? d_body : d, plan.n, plan.n_tiles,
                                  static_cast<TileRecord *>(ws.d_records.p), grp, prm.hot, tie_lists(ws, plan),
                                  static_cast<uint32_t *>(ws.d_ctr.p), prm.epoch, ts,
                                  ch->timing ? ev[1] : nullptr,
@@ -540,15 +622,37 @@ int upload_and_launch(rc_chunker *ch, Workspace &ws, const Plan &plan, ChainPara
         return abandon_launch(ws, ts, xs, rc_fail(RC_ERR_HIP, "hipEventRecord failed"));
     const uint32_t join = (ch->knobs[knJoinWalk] ? RC_JOIN_WALK_ONLY : 0u) |
                           (ch->knobs[knRepair] ? RC_JOIN_REPAIR : 0u);
-    if (int rc = rc_launch_chain(ch->d_tables, d, plan.n, prm, plan.n_segs,
-                                 static_cast<const TileRecord *>(ws.d_records.p), d_cuts, d_counts,
-                                 static_cast<uint64_t *>(ws.d_scratch.p),
-                                 static_cast<uint64_t *>(ws.d_seg_counts.p), plan.any_multi, join, xs))
-        return abandon_launch(ws, ts, xs, rc);
+    // the rounds' scanned-tile counts (rc_chunker_tail_scanned): zeroed once per call
+    if (rounds && hipMemsetAsync(scanned, 0, 4 * kCtrScannedWords, xs) != hipSuccess)
+        return abandon_launch(ws, ts, xs, rc_fail(RC_ERR_HIP, "hipMemsetAsync failed"));
+    // A lazy call: the chain walks as far as the body's records reach, then `rounds` times the
+    // windowed tile launch reads what the stopped chains ask for and the chain resumes; the
+    // last round is the closing round, whose window is every tail tile not read yet, so the
+    // chain launch after it finishes every stream.  All on the chain stream; the host planned
+    // the tail units once and never reads the state.
+    for (uint32_t r = 0; r <= rounds; ++r) {
+        if (r) {
+            win.closing = r == rounds ? 1u : 0u;
+            win.scanned = scanned + (r - 1);
+            if (int rc = rc_launch_tail_round(ch->d_tables, d_tail, d_tedge, plan.n, plan.n_tail, win,
+                                              static_cast<TileRecord *>(ws.d_records.p),
+                                              tail_tie_lists(ws, plan),
+                                              static_cast<uint32_t *>(ws.d_ctr.p), prm.epoch, xs,
+                                              ch->reserve, ch->sched))
+                return abandon_launch(ws, ts, xs, rc);
+        }
+        prm.lz_final = r == rounds ? 1u : 0u;
+        if (int rc = rc_launch_chain(ch->d_tables, d, plan.n, prm, plan.n_segs,
+                                     static_cast<const TileRecord *>(ws.d_records.p), d_cuts, d_counts,
+                                     static_cast<uint64_t *>(ws.d_scratch.p),
+                                     static_cast<uint64_t *>(ws.d_seg_counts.p), plan.any_multi, join, xs))
+            return abandon_launch(ws, ts, xs, rc);
+    }
     if (hipEventRecord(ws.done, xs) != hipSuccess)
         return abandon_launch(ws, ts, xs, rc_fail(RC_ERR_HIP, "hipEventRecord failed"));
     ws.pending = true;
     ws.piped = pipelined;
+    ws.lazy_rounds = rounds;
     if (ch->timing) {
         RC_HIP_TRY(hipEventRecord(ev[3], xs));
         ch->ev_rec.push_back(ev);
@@ -641,6 +745,8 @@ ChainParams chain_params(const rc_chunker *ch, const Plan &plan, uint64_t max_st
     p.hot = 0;
     p.fault = nullptr;  // set per launch (upload_and_launch)
     p.epoch = 0;
+    p.lz = LazyState{nullptr, nullptr, nullptr, nullptr};  // set per lazy call (upload_and_launch)
+    p.lz_final = 0;
     return p;
 }
 
@@ -681,6 +787,34 @@ uint64_t rc_keys_needed(uint64_t max_length, uint64_t L, uint64_t P) {
     if (!any) return 0;
     const uint64_t jneed = bound / 4 + T, jmax = (L - 4) / 4;
     return std::min(jneed, jmax);
+}
+
+int rc_lazy_tail_split(uint64_t max_length, uint64_t L, uint64_t P, uint64_t *tiles,
+                       uint64_t *body_tiles) {
+    if (!tiles || !body_tiles) return rc_fail(RC_ERR_ARGUMENT, "null argument");
+    const uint64_t jneed = rc_keys_needed(max_length, L, P);
+    uint64_t bound = 0;
+    *tiles = *body_tiles = 0;
+    if (!jneed || !argmax_bound(max_length, L, P, bound)) return RC_OK;  // the tail rule only
+    *tiles = jneed / kTileKeys + 1;
+    // the body: through the tile of the key at the last chunk start with an argmax
+    *body_tiles = std::min(*tiles, bound / 4 / kTileKeys + 1);
+    return RC_OK;
+}
+
+int rc_chunker_tail_scanned(rc_chunker *ch, uint32_t *rounds, uint64_t *scanned, uint64_t cap) {
+    if (!ch || !rounds) return rc_fail(RC_ERR_ARGUMENT, "null argument");
+    std::lock_guard<std::mutex> lock(ch->mu);
+    DeviceGuard g(ch->device);
+    Workspace &ws = ch->ws[(ch->next_ws - 1) & 1];
+    *rounds = ws.lazy_rounds;
+    if (ws.pending) RC_HIP_TRY(hipEventSynchronize(ws.done));
+    uint32_t h[kCtrScannedWords] = {};
+    if (ws.lazy_rounds)
+        RC_HIP_TRY(hipMemcpy(h, static_cast<uint32_t *>(ws.d_ctr.p) + kCtrScannedWord, sizeof h,
+                             hipMemcpyDeviceToHost));
+    for (uint32_t r = 0; r < ws.lazy_rounds && r < cap && scanned; ++r) scanned[r] = h[r];
+    return RC_OK;
 }
 
 int rc_chunker_create(uint64_t min_length, uint64_t max_length, const uint8_t *key,
@@ -929,8 +1063,14 @@ int rc_chunk_device(rc_chunker *ch, uint64_t n, const uint8_t *const *d_streams,
     ch->pipelined_calls += pipelined ? 1 : 0;
     Plan plan;
     Workspace &ws = acquire_ws(ch);
+    // Lazy tails: pipelined calls that another call may follow, on the large-window path
+    // (rc_spec_kernel<R, false>, no group records), when every stream is one chain segment
+    // (stage_descriptors).  A sequential or END call would pay the rounds' launches in the open.
+    const bool lazy_ok = pipelined && !(flags & RC_PIPELINE_END) && !open && !ch->small &&
+                         !ch->groups && ch->window / kTileKeys + 3 > 64 &&
+                         ch->knobs[knTailRounds] > 0;
     if (int rc = stage_descriptors(ch, ws, n, d_streams, lens, last_piece, plan, open, false,
-                                   pipelined ? 16ull * ch->reserve : 0))
+                                   pipelined ? 16ull * ch->reserve : 0, lazy_ok))
         return rc;
     return upload_and_launch(ch, ws, plan, chain_params(ch, plan, ~0ull, flags), d_cuts, d_counts,
                              static_cast<hipStream_t>(hip_stream), pipelined,

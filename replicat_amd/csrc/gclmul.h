@@ -93,6 +93,30 @@ __host__ __device__ inline uint32_t group_hot_threshold(uint64_t window) {
     return below >= 65536 ? 0u : (uint32_t)(65536 - below);
 }
 
+// Lazy tails (capi.cpp upload_and_launch): the per-stream state of a call whose
+// tail tiles are read in rounds on the chain stream, n_streams u64 each, in device memory.
+//   have   keys whose records the chain may use: every tile below have / kTileKeys is done
+//          (a multiple of kTileKeys; kLazyDone once the stream's count is written)
+//   want   the keys the stream's next window needs, rounded up to a tile: the next round reads
+//          the tail tiles [have, want) / kTileKeys
+//   pos, ncut  where the chain stopped: its next chunk start and its cuts so far
+// The host writes the first state with the descriptors and never reads it back; the chain
+// launches update it, the windowed tile launches read have / want.
+constexpr uint64_t kLazyDone = ~0ull;
+struct LazyState {
+    uint64_t *have, *want, *pos, *ncut;
+};
+
+// What a windowed tile launch (rc_tile_kernel<.., TileWindow>) knows beside its descriptors.
+struct TileWindow {
+    const uint64_t *have, *want;  // LazyState
+    const uint64_t *body;         // tiles of each stream the body launch took: its first tail tile
+    const uint64_t *rec_off;      // record index of a stream's launch tile t: t + rec_off[s]
+    uint64_t spare;               // the call's spare record (its tile count: rc_launch_tiles)
+    uint32_t *scanned;            // += the tiles this launch scanned (one add per wave)
+    uint32_t closing;             // the closing round: the window is everything from have on
+};
+
 struct ChainParams {
     uint64_t min_length;
     uint64_t max_length;
@@ -113,6 +137,11 @@ struct ChainParams {
     // records are incomplete, and the chain kernels write RC_COUNT_FAULT instead of cuts
     const uint64_t *fault;
     uint64_t epoch;
+    // lazy tails (rc_spec_kernel<.., kLazy = true>): the chain resumes from lz.pos / lz.ncut and
+    // stops before a step whose window ends at or past lz.have (lz.pos NULL: an ordinary call);
+    // lz_final: the launch after the closing round, when every record is there
+    LazyState lz;
+    uint32_t lz_final;
 };
 
 // The tile kernel's counter buffer (256 bytes per workspace, capi.cpp ensure_ctr), in u32 words:
@@ -121,7 +150,9 @@ struct ChainParams {
 //                the edge kernel moves it into the stamp below and clears it
 //   kCtrStampWord (u64) the epoch of the last call whose tile kernel set the flag
 //   kCtrFaultsWord how many calls set it since the last rc_chunker_check
+//   kCtrScannedWord .. + kCtrScannedWords  lazy calls: the tiles each tail round scanned
 constexpr uint32_t kCtrErrWord = 32, kCtrStampWord = 34, kCtrFaultsWord = 36;
+constexpr uint32_t kCtrScannedWord = 8, kCtrScannedWords = 16;
 // Count written for every stream of a faulted call (include/replicat_chunker.h RC_COUNT_FAULT;
 // -1 is a capacity overflow, -2 the chain kernels' internal kNeedJoin)
 constexpr int64_t kCountFault = -3;
@@ -167,6 +198,16 @@ int rc_launch_tiles(const rc::KeyTables *d_tables, rc::StreamDesc desc, uint64_t
                     uint32_t hot, uint32_t *d_xlist, uint32_t *d_ctr, uint64_t epoch,
                     void *stream, void *mid_event, uint32_t cus, void *edge_stream, void *tiled,
                     rc::TileSched sched);
+// One tail round of a lazy call (capi.cpp upload_and_launch): the windowed tile kernel over the
+// call's n_tail_tiles tail tiles (tail_desc: desc with tile_base = the prefix sum of the tail
+// tile counts), then its edge kernel (desc: the call's, with xtiles = the tail tiles that are
+// not fast), both on `stream`, the tile kernel's grid sized to `cus`.  d_xlist:
+// rc_tie_list_words(n_tail_tiles) words of the round's own.  d_ctr: as rc_launch_tiles.
+int rc_launch_tail_round(const rc::KeyTables *d_tables, rc::StreamDesc tail_desc,
+                         rc::StreamDesc desc, uint64_t n_streams, uint64_t n_tail_tiles,
+                         rc::TileWindow win, rc::TileRecord *d_records, uint32_t *d_xlist,
+                         uint32_t *d_ctr, uint64_t epoch, void *stream, uint32_t cus,
+                         rc::TileSched sched);
 uint64_t rc_tie_list_words(uint64_t n_tiles);
 // (exported for tests: include/replicat_chunker.h rc_tile_schedule)
 // join: RC_JOIN_* bits -- how multi-segment streams are spliced

@@ -460,13 +460,24 @@ __device__ __forceinline__ uint32_t wave_max_pk16(uint32_t v) {
 // 256-key slices up to the stream's last needed key, not 16: the ring reads only those (the
 // buffer resource's range ends there) and the scan masks the rest -- config 3 (iii)'s 1 MiB
 // streams need 2 of their last tile's 16 slices, 1.5 % of the bytes the kernel read before.
-template <bool kCache, bool kClip = false>
+//
+// kWin (lazy tails, capi.cpp upload_and_launch): the launch runs over the streams' TAIL tiles
+// only -- d.tile_base is the prefix sum of the tail tile counts, a stream's launch tile i is its
+// tile win.body[s] + i -- and takes of them those inside the round's window, stream tiles
+// [have[s], want[s]) / kTileKeys (the closing round: from have[s] on).  A tile outside the
+// window is stepped over like a tile that is not fast.  The window words are loaded when the
+// cursor enters the stream, like the pointer and the length.
+template <bool kCache, bool kClip = false, bool kWin = false>
 struct TileCursor {
     StreamDesc d;
     uint64_t s, cur, next;
     const uint8_t *base;
     uint32_t nfast;  // the stream's tiles 0 .. nfast - 1 are on the fast path (tile_fast)
     uint32_t nlast;  // kClip: the slices of the stream's last tile holding needed keys
+    TileWindow win;      // kWin
+    uint32_t wlo, whi;   // kWin: the stream's launch tiles [wlo, whi) are fast tiles of the window
+    uint64_t jbase;      // kWin: first key of the stream's launch tile 0
+    uint64_t roff;       // kWin: record index of the stream's launch tile t = t + roff
     __device__ void enter() {
         if constexpr (!kCache) return;
         base = sload_ptr(d.ptr + s);
@@ -477,6 +488,16 @@ struct TileCursor {
         if constexpr (kClip) {
             const uint64_t jl = sload(d.jneed + s) - (next - cur - 1) * kTileKeys;
             nlast = jl < (uint64_t)kTileKeys ? (uint32_t)(jl >> 8) + 1u : (uint32_t)kTileIters;
+        }
+        if constexpr (kWin) {
+            const uint64_t nb = sload(win.body + s);
+            const uint64_t lo = sload(win.have + s) / kTileKeys;
+            const uint64_t hi = win.closing ? ~0ull : sload(win.want + s) / kTileKeys;
+            const uint64_t a = max(lo, nb), b = min(hi, (uint64_t)nfast);
+            wlo = (uint32_t)(a - nb);  // a finished stream has have = ~0: an empty window
+            whi = b > a ? (uint32_t)(b - nb) : wlo;
+            jbase = nb * kTileKeys;
+            roff = sload(win.rec_off + s);
         }
     }
     __device__ void init(const StreamDesc &dd, uint64_t n_streams, uint64_t t) {
@@ -504,7 +525,12 @@ struct TileCursor {
         TileRef r;
         r.j0 = (t - cur) * kTileKeys;
         r.s = (uint32_t)s;
-        if constexpr (kCache) {
+        if constexpr (kWin) {
+            static_assert(kCache && !kClip, "the windowed cursor caches and does not clip");
+            r.j0 += jbase;
+            r.base = base;
+            r.fast = t - cur >= wlo && t - cur < whi ? (uint32_t)kTileIters : 0u;
+        } else if constexpr (kCache) {
             r.base = base;
             r.fast = t - cur < nfast ? (kClip && t + 1 == next ? nlast : (uint32_t)kTileIters) : 0u;
         } else {
@@ -514,6 +540,10 @@ struct TileCursor {
         return r;
     }
 };
+
+// the window of a windowed launch's trailing argument pack (none: never read)
+__device__ __forceinline__ TileWindow window_of() { return TileWindow{}; }
+__device__ __forceinline__ TileWindow window_of(const TileWindow &w) { return w; }
 
 __device__ __forceinline__ void stage_tile_tables_nb(const KeyTables *tab) {
     // the 32x replicated prefilter tables and the exact tables.  Each thread loads its table
@@ -766,7 +796,13 @@ struct UnitGrab {
 //
 // The grab for a wave's next unit is issued when it enters a unit and read when it leaves it,
 // so the atomic's latency hides behind the unit's tiles.  ctr must be 0 at launch.
-template <int G, bool kGroup>
+//
+// kWin: a tail round of a lazy call (TileCursor): the launch's tiles are the streams' tail tiles,
+// of which only those in the round's window are scanned; records and tie lists carry the record
+// index (launch tile + TileWindow::rec_off), so the edge and chain kernels find them where an
+// ordinary launch puts them.  The window is a trailing argument only these instances have (W =
+// TileWindow), so the instances without one keep their signature and their code.
+template <int G, bool kGroup, typename... W>
 __global__ __launch_bounds__(1024) void rc_tile_kernel(const KeyTables *__restrict__ tab,
                                                        StreamDesc d, uint64_t n_streams,
                                                        TileUnits U,
@@ -775,7 +811,10 @@ __global__ __launch_bounds__(1024) void rc_tile_kernel(const KeyTables *__restri
                                                        uint32_t hot,
                                                        uint32_t *__restrict__ xlist,
                                                        uint32_t *__restrict__ xcount,
-                                                       uint32_t *__restrict__ ctr) {
+                                                       uint32_t *__restrict__ ctr, W... window) {
+    constexpr bool kWin = sizeof...(W) != 0;
+    static_assert(!kWin || G == 1, "windowed launches: large windows only (no group records)");
+    const TileWindow wnd = window_of(window...);
     UnitGrab<kGroup> grab;
     grab.start(U, ctr);
     stage_tile_tables_nb(tab);
@@ -795,7 +834,10 @@ __global__ __launch_bounds__(1024) void rc_tile_kernel(const KeyTables *__restri
     RC_TILE_STAMP_BEGIN();
 
     // the first fast tile, possibly in a later unit (units without one list no ties)
-    TileCursor<true, (G > 1)> cursor;
+    TileCursor<true, (G > 1), kWin> cursor;
+    uint64_t cur_roff = 0, nx_roff = 0;  // kWin: record index - launch index of cur and nx
+    uint32_t n_scanned = 0;              // kWin: tiles this wave scanned
+    if constexpr (kWin) cursor.win = wnd;
     TileRef cur;
     uint64_t t = ub;
     bool seek = true;
@@ -804,6 +846,7 @@ __global__ __launch_bounds__(1024) void rc_tile_kernel(const KeyTables *__restri
             if (seek) cursor.init(d, n_streams, t);
             seek = false;
             cur = cursor.at(t);
+            if constexpr (kWin) cur_roff = cursor.roff;
             if (cur.fast) break;
             ++t;
             continue;
@@ -832,6 +875,7 @@ __global__ __launch_bounds__(1024) void rc_tile_kernel(const KeyTables *__restri
     // neighbour word, candidate words, one record store) so the compiler's in-order vmcnt
     // waits stay exact; the first store goes to the spare record at n_tiles.
     uint64_t pend_t = n_tiles;  // SGPRs: the pending tile,
+    if constexpr (kWin) pend_t = wnd.spare;  // (the spare record of the call's record array)
     uint64_t pend_jm = 0;       // its first key | its top-16 maximum M << 48 (j0 < 2^44),
     uint64_t pend_mask = 0;     // a marker's candidate lanes, else the lanes holding a key
     uint32_t pend_st = 0;       // bit 31: a marker record, low bits: the stream
@@ -874,6 +918,7 @@ __global__ __launch_bounds__(1024) void rc_tile_kernel(const KeyTables *__restri
         for (;;) {
             if (tn < nue) {
                 nx = cursor.at(tn);
+                if constexpr (kWin) nx_roff = cursor.roff;
                 if (nx.fast) break;
                 ++tn;
                 continue;
@@ -920,9 +965,10 @@ __global__ __launch_bounds__(1024) void rc_tile_kernel(const KeyTables *__restri
                 if ((lane >> 2) == q) jl = f * 256 + c * 4 + (lane & 3);
             }
         }
-        if (lane == 0) xlist[ub + n_ties] = (uint32_t)t;  // kept only if it is a tie
+        if (lane == 0) xlist[ub + n_ties] = (uint32_t)(t + cur_roff);  // kept only if it is a tie
         n_ties += tie ? 1u : 0u;
-        pend_t = t;
+        pend_t = t + cur_roff;
+        if constexpr (kWin) ++n_scanned;
         pend_jm = cur.j0 | ((uint64_t)M << 48);
         pend_mask = tie ? cmask : (nc >= 16 ? ~0ull : (1ull << (4 * nc)) - 1);
         pend_st = (tie ? 0x80000000u : 0u) | (uint32_t)cur.s;
@@ -941,10 +987,12 @@ __global__ __launch_bounds__(1024) void rc_tile_kernel(const KeyTables *__restri
         if (!nx.fast) break;
         t = tn;
         cur = nx;
+        if constexpr (kWin) cur_roff = nx_roff;
     }
     retire();
     if (lane == 0) {
         xcount[u] = n_ties;
+        if constexpr (kWin) atomicAdd(wnd.scanned, n_scanned);
         RC_TILE_STAMP_END(gw);
     }
 }
@@ -1016,6 +1064,11 @@ __device__ __forceinline__ void exact_lanes(const uint64_t *tl, const uint64_t *
 // the tile kernel's waves (xlist / xcount), the rest the host's list of tiles the fast path
 // does not take (tile_fast: the stream ends inside the tile; d.xtiles).  Each is recomputed
 // over the same key range the fast path would have covered (tile_key_end).
+// kWin: after a windowed tile launch (a tail round of a lazy call).  The tie lists hold record
+// indices, as always; d.tile_base is the call's, d.xtiles the host's list of the TAIL tiles that
+// are not fast, of which the round settles those inside its window -- so a last tile that runs
+// past the stream's final word is computed in the first round that contains it.
+template <typename... W>
 __global__ __launch_bounds__(256) void rc_edge_kernel(const KeyTables *__restrict__ tab,
                                                       StreamDesc d, uint64_t n_streams,
                                                       TileUnits U,
@@ -1023,7 +1076,10 @@ __global__ __launch_bounds__(256) void rc_edge_kernel(const KeyTables *__restric
                                                       GroupRecord *__restrict__ grp,
                                                       const uint32_t *__restrict__ xlist,
                                                       const uint32_t *__restrict__ xcount,
-                                                      uint32_t *__restrict__ ctr, uint64_t epoch) {
+                                                      uint32_t *__restrict__ ctr, uint64_t epoch,
+                                                      W... window) {
+    constexpr bool kWin = sizeof...(W) != 0;
+    const TileWindow win = window_of(window...);
     __shared__ __attribute__((aligned(16))) uint64_t s_full[2048];
     __shared__ uint32_t s_fault;
     // The tile kernel is done with its grab counter: zero it for the workspace's next launch
@@ -1095,7 +1151,14 @@ __global__ __launch_bounds__(256) void rc_edge_kernel(const KeyTables *__restric
                 }
             } else {
                 const uint64_t t = sload(d.xtiles + 1 + (e - n_units));
-                exact_tile(tl, th, d, stream_of_tile(d, n_streams, t), t, rec, grp);
+                const uint64_t s = stream_of_tile(d, n_streams, t);
+                if constexpr (kWin) {
+                    const uint64_t k = t - sload(d.tile_base + s);
+                    if (k < sload(win.have + s) / kTileKeys ||
+                        (!win.closing && k >= sload(win.want + s) / kTileKeys))
+                        continue;
+                }
+                exact_tile(tl, th, d, s, t, rec, grp);
             }
         }
     }
@@ -1678,7 +1741,14 @@ __device__ __forceinline__ uint64_t find_index(const uint64_t *base_arr, uint64_
 // Workgroups of kChainWaves walkers on 20 KiB of LDS.  R = rows of the record cache: 1 for
 // windows of up to ~60 tiles (max_length below ~1 MB: a 1 MiB stream's records load once),
 // 4 otherwise (a default window spans 313 tiles and reloads every step, as it must).
-template <int R, bool kLean>
+//
+// kLazy (lazy tails, every stream one segment): the launch is one of a sequence over the same
+// streams.  It resumes each chain where the launch before stopped (prm.lz.pos / ncut), and stops
+// a chain before a step whose window ends at or past the keys whose records exist so far -- what
+// the tile launch before it read, the stream's `want` -- leaving the window's end, rounded up to
+// a tile, as the next `want`.  The launch that finishes a stream writes its count and marks it
+// done (kLazyDone); the launches after it pass it by.  prm.lz_final: every record exists.
+template <int R, bool kLean, bool kLazy = false>
 __global__ __launch_bounds__(kChainWaves * 64) void rc_spec_kernel(const KeyTables *__restrict__ tab,
                                                       StreamDesc d, uint64_t n_streams,
                                                       ChainParams prm, uint64_t n_segs,
@@ -1714,6 +1784,14 @@ __global__ __launch_bounds__(kChainWaves * 64) void rc_spec_kernel(const KeyTabl
 
     uint64_t pos = i * prm.seg_bytes, n = 0, ext = 0;
     bool overflow = false, term = false;
+    uint64_t have = ~0ull, want = 0;  // kLazy
+    bool suspend = false;
+    if constexpr (kLazy) {
+        pos = sload(prm.lz.pos + s);
+        if (pos == kLazyDone) return;
+        n = sload(prm.lz.ncut + s);
+        if (!prm.lz_final) have = sload(prm.lz.want + s);  // the round before read up to it
+    }
     RecCache<R> cache;
     auto emit = [&](uint64_t c) {
         if (n >= cap) {
@@ -1729,6 +1807,16 @@ __global__ __launch_bounds__(kChainWaves * 64) void rc_spec_kernel(const KeyTabl
             break;
         }
         if (!direct && pos >= seg_end && ext++ >= prm.ext_steps) break;
+        if constexpr (kLazy) {  // chain_step's argmax test and window end
+            const bool argmax = (st.P >= pos && st.P - pos >= prm.max_length) ||
+                                st.L - pos >= 2 * prm.max_length;
+            const uint64_t jb = min((pos >> 2) + prm.window, st.jmax);
+            if (argmax && jb >= have) {
+                suspend = true;
+                want = (jb / kTileKeys + 1) * kTileKeys;
+                break;
+            }
+        }
         uint64_t c1 = 0, c2 = 0;
         int kind;
         if constexpr (kLean) {
@@ -1749,6 +1837,16 @@ __global__ __launch_bounds__(kChainWaves * 64) void rc_spec_kernel(const KeyTabl
         }
         if (overflow) break;
         pos = c1;
+    }
+    if constexpr (kLazy) {
+        if (lane == 0) {
+            prm.lz.have[s] = suspend ? have : kLazyDone;
+            prm.lz.want[s] = suspend ? want : kLazyDone;
+            prm.lz.pos[s] = suspend ? pos : kLazyDone;
+            prm.lz.ncut[s] = n;
+            if (!suspend) counts[s] = overflow ? -1 : (int64_t)n;
+        }
+        return;
     }
     if (lane == 0) {
         if (direct) {
@@ -2708,10 +2806,39 @@ int rc_launch_tiles(const KeyTables *d_tables, StreamDesc desc, uint64_t n_strea
     uint64_t egrid = (U.n_units + 3) / 4;
     if (egrid > 4 * cus) egrid = 4 * cus;
     if (egrid == 0) egrid = 1;
-    hipLaunchKernelGGL(rc_edge_kernel, dim3((unsigned)egrid), dim3(256), 0, est, d_tables, desc,
+    hipLaunchKernelGGL(rc_edge_kernel<>, dim3((unsigned)egrid), dim3(256), 0, est, d_tables, desc,
                        n_streams, U, d_records, d_grp, (const uint32_t *)d_xlist,
                        (const uint32_t *)d_xcount, d_ctr, epoch);
     return launch_status("rc_edge_kernel");
+}
+
+int rc_launch_tail_round(const KeyTables *d_tables, StreamDesc tail_desc, StreamDesc desc,
+                         uint64_t n_streams, uint64_t n_tail_tiles, TileWindow win,
+                         TileRecord *d_records, uint32_t *d_xlist, uint32_t *d_ctr, uint64_t epoch,
+                         void *stream, uint32_t cus, TileSched sched) {
+    if (n_tail_tiles == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t waves_per_wg = 1024 / kWaveSize;
+    uint64_t grid = (n_tail_tiles + waves_per_wg - 1) / waves_per_wg;
+    if (grid > cus) grid = cus;  // persistent, on the stream's (reserved) CUs
+    const TileUnits U = tile_units(n_tail_tiles, grid * waves_per_wg, sched);
+    uint32_t *d_xcount = d_xlist + n_tail_tiles;
+    if (U.n_groups != 0)
+        hipLaunchKernelGGL((rc_tile_kernel<1, true, TileWindow>), dim3((unsigned)grid), dim3(1024), 0, st,
+                           d_tables, tail_desc, n_streams, U, d_records, (GroupRecord *)nullptr, 0u,
+                           d_xlist, d_xcount, d_ctr, win);
+    else
+        hipLaunchKernelGGL((rc_tile_kernel<1, false, TileWindow>), dim3((unsigned)grid), dim3(1024), 0, st,
+                           d_tables, tail_desc, n_streams, U, d_records, (GroupRecord *)nullptr, 0u,
+                           d_xlist, d_xcount, d_ctr, win);
+    if (int rc = launch_status("rc_tile_kernel (tail round)")) return rc;
+    uint64_t egrid = (U.n_units + 3) / 4;
+    if (egrid > 4 * (uint64_t)cus) egrid = 4 * (uint64_t)cus;
+    if (egrid == 0) egrid = 1;
+    hipLaunchKernelGGL(rc_edge_kernel<TileWindow>, dim3((unsigned)egrid), dim3(256), 0, st, d_tables, desc,
+                       n_streams, U, d_records, (GroupRecord *)nullptr, (const uint32_t *)d_xlist,
+                       (const uint32_t *)d_xcount, d_ctr, epoch, win);
+    return launch_status("rc_edge_kernel (tail round)");
 }
 
 int rc_tile_schedule(uint64_t n_tiles, uint32_t waves, uint32_t permille, uint32_t chunk,
@@ -2739,6 +2866,16 @@ int rc_launch_chain(const KeyTables *d_tables, StreamDesc desc, uint64_t n_strea
                     uint64_t *d_seg_counts, bool any_multi, uint32_t join, void *stream) {
     if (n_streams == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
+    if (prm.lz.pos) {  // one launch of a lazy call's sequence: large windows, one segment each
+        if (any_multi || n_segs != n_streams || prm.lean || prm.grp || prm.max_steps == 0)
+            return rc_fail(RC_ERR_ARGUMENT, "lazy tails: not a large-window one-segment call");
+        const uint64_t grid = (n_segs + kChainWaves - 1) / kChainWaves;
+        hipLaunchKernelGGL((rc_spec_kernel<kRecUnroll, false, true>), dim3((unsigned)grid),
+                           dim3(kChainWaves * kWaveSize), 0, st, d_tables, desc, n_streams, prm,
+                           n_segs, d_records, d_cuts, d_counts, d_scratch, d_seg_counts,
+                           d_seg_counts);
+        return launch_status("rc_spec_kernel (lazy)");
+    }
     // many single-segment streams with small windows and group bounds: a quad of lanes per stream
     if (prm.lane && prm.lean && prm.grp && !any_multi && n_segs == n_streams &&
         prm.max_steps != 0 && prm.window / kTileKeys <= (uint64_t)kLaneFull) {

@@ -40,6 +40,9 @@ enum Knob : int {
     knTileGroup,      // RC_TILE_GROUP
     knTileMask,       // RC_TILE_MASK
     knHostBatchBytes, // RC_HOST_BATCH_BYTES
+    knTailRounds,     // RC_TAIL_ROUNDS
+    knTailShare,      // RC_TAIL_SHARE
+    knCutCapMax,      // RC_CUT_CAP_MAX
     kKnobCount
 };
 
@@ -111,6 +114,19 @@ inline constexpr KnobSpec kKnobTable[kKnobCount] = {
      "rc_chunk_host / rc_chunk_digest_host: bytes of whole streams per double-buffered batch "
      "(a stream longer than this is a batch of its own); test switch: a small value sends a "
      "few MiB through many batches, so the suite can check slot reuse and output offsets"},
+    {"RC_TAIL_ROUNDS", 3, 0, 16, nullptr,
+     "lazy tails: pipelined large-window calls read each stream's last max_length or so in this "
+     "many rounds on the chain stream, each round only as far as the stopped chains' next "
+     "windows reach, the last one whatever is left (1: that round alone); 0: every call reads "
+     "all its tiles in the one tile launch"},
+    {"RC_TAIL_SHARE", 100, 0, int64_t(1) << 30, nullptr,
+     "lazy tails: a call is lazy only when its tail tiles are at most this many per mille of "
+     "its body tiles, so that the rounds fit beside the next body launch (100: streams of about "
+     "12 max_lengths or more; the suite raises it to run the rounds on short streams)"},
+    {"RC_CUT_CAP_MAX", 0, 0, int64_t(1) << 40, nullptr,
+     "test switch: the kernels see at most this cut capacity per stream (0: no limit; the "
+     "arrays keep the layout of rc_cut_capacity), so the suite can check that a stream whose "
+     "cuts do not fit reports RC_COUNT_OVERFLOW"},
 };
 // clang-format on
 
