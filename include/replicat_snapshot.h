@@ -406,6 +406,95 @@ int rc_snapshot_strip_parts_device(rc_snapshot *s, uint64_t n, const void *d_des
 int rc_snapshot_read_timing_read(rc_snapshot *s, double *find_ms, double *parse_ms, double *sums_ms,
                                  double *strip_ms, uint64_t *find_calls);
 
+/* ---------------------------------------------------------------------------------------------
+ * Reading the files' text: the way back of "Writing the files' text", from the stripped text
+ * stage 4 of "Reading `data`" leaves on the device to the columns of every file -- path bytes and
+ * offsets, digest slots, the unfinished flag, the seven metadata integers.  The input is what
+ * stage 4 left: the stripped texts at their places in d_out (d_desc says where), d_stripped_len,
+ * d_run_close, d_text_run_first and the parts' d_status.  In a canonical text run r of a text is
+ * the list of its file r, so FILES are numbered as runs are, across the texts of a call, and
+ * `runs` -- d_text_run_first[n], which the host knows after its first synchronisation -- sizes the
+ * arrays per file and the grids.
+ *
+ * With R > 0 runs, text i divides at the ']' positions c[0 .. R - 1] = d_run_close into R + 1
+ * pieces, as the writer's section describes them:
+ *     piece 0 = first + head(0)                  first = {"utc_timestamp":"S","files":[
+ *     piece j = ] + tail(j - 1) + }, + head(j)   head  = {"path":"Q","chunks":[
+ *     piece R = ] + tail(R - 1) + }] + last      tail  = ,"digest":D[,"metadata":M]
+ * The device accepts a piece only if it is exactly this, byte for byte, with nothing left over:
+ * this strictness takes the place of the JSON round trip on the host.  Every "chunks":[ stage 1
+ * saw is then proven to be a file's list, in order, because each one ends a head that was parsed
+ * strictly.
+ *   first  the 18 bytes {"utc_timestamp":" , a string body up to its first unescaped quote, then
+ *          ,"files":[ ; its length goes to d_first_len[i].  The string's contents and all of
+ *          `last` (the text behind the ']' of files, from d_last_off[i]) are the host's to judge:
+ *          deserialize(first + ']' + last) must be a dict with files == [] that serialises to
+ *          those bytes again.  A first longer than 4096 bytes is not accepted.
+ *   D      null, or {"!b":"B"} with B the canonical base64 of exactly digest_size bytes: the
+ *          standard alphabet, 4 ceil(digest_size / 3) characters with the padding that implies,
+ *          and zero trailing bits.  The bytes go to the file's 64-byte slot, zeros behind them;
+ *          a null D leaves the slot all zero.
+ *   M      present in every file of a text or in none (d_has_metadata[i]).  null, or
+ *          {"st_mode":a,"st_uid":b,"st_gid":c,"st_size":d,"st_atime_ns":e,"st_mtime_ns":f,"st_ctime_ns":g}
+ *          with canonical signed decimals: an optional '-', then 1 to 19 digits, no leading zero,
+ *          no -0, within int64.  D and M are both null or both not: the writer's one flag,
+ *          d_unfinished[f].  A file without values has a row of zeros.
+ *   Q      what json's encode_basestring_ascii writes and nothing else json.loads would also
+ *          take: raw bytes 0x20..0x7e except " and \ ; the escapes \" \\ \b \f \n \r \t ; \uxxxx
+ *          with lowercase digits whose code is below 0x20 and has no short form, is 0x7f, or is
+ *          at least 0x80.  A dangling backslash, \/ , \u0041, \u0008 and an uppercase digit are
+ *          refused.  Q opens behind {"path":" and closes 12 bytes before c[j], where ","chunks":[
+ *          must stand, so no unescaped quote may lie inside.  Q decodes to the bytes of
+ *          str.encode('utf-8', 'surrogatepass') of what json.loads returns: one, two or three
+ *          bytes per code unit, lone surrogates included, and four for a high surrogate with a \u
+ *          low surrogate directly behind it, which json.loads joins.  A decoded path is never
+ *          longer than its text.
+ * Anything else stores RC_FILES_NOT_CANONICAL into d_file_status[i]; the text's other results
+ * then mean nothing, and no other text's result is touched.  A text whose parts status is not
+ * RC_PARTS_OK is skipped and gets RC_FILES_NOT_CANONICAL as well; a text with no runs gets
+ * RC_FILES_OK and zero files, and all of it stays with the host.  Nothing outside the arrays is
+ * read or written: offsets are clamped to the piece, as the writer clamps.
+ *
+ * Two calls on the same handle, each enqueued on hip_stream without a synchronisation; all arrays
+ * are DEVICE memory.  RC_ERR_ARGUMENT: a NULL handle or array, digest_size outside 1..64, n or runs
+ * of 2^32 or more.  Kernels: replicat_amd/csrc/snapshot_fields.hip.
+ * ------------------------------------------------------------------------------------------- */
+
+#define RC_FILES_OK 0
+#define RC_FILES_NOT_CANONICAL 2 /* RC_PARTS_NOT_CANONICAL's value */
+
+/* Host only: the bytes Q decodes to, for the `len` bytes of Q at `text` (without its quotes), or
+ * UINT64_MAX when Q is not canonical. */
+uint64_t rc_snapshot_path_bytes_for(const uint8_t *text, uint64_t len);
+
+/* The fields pass and the scan.  Per text (n entries each): d_file_status (bytes), d_has_metadata
+ * (bytes), d_first_len and d_last_off (words of 64 bits).  Per file: d_digests (64-byte slots,
+ * `runs` of them), d_unfinished (bytes), d_metadata (7 int64 each), d_path_text (where Q starts in
+ * its stripped text; the path pass reads it) and d_path_off (runs + 1 words: path f will be the
+ * bytes d_path_off[f] .. d_path_off[f + 1] - 1, the total in the last). */
+int rc_snapshot_parse_files_device(rc_snapshot *s, uint64_t n, const void *d_desc, uint64_t runs,
+                                   const uint64_t *d_text_run_first, const uint64_t *d_run_close,
+                                   const uint64_t *d_stripped_len, const uint8_t *d_status,
+                                   const uint8_t *d_out, uint32_t digest_size, uint8_t *d_file_status,
+                                   uint8_t *d_has_metadata, uint64_t *d_first_len, uint64_t *d_last_off,
+                                   uint8_t *d_digests, uint8_t *d_unfinished, int64_t *d_metadata,
+                                   uint64_t *d_path_text, uint64_t *d_path_off, void *hip_stream);
+
+/* The path pass: Q of every file of a text with RC_FILES_OK, decoded to d_path_bytes +
+ * d_path_off[f].  d_path_bytes has path_room bytes, and the summed stripped lengths are enough;
+ * no byte at or behind path_room is written.  The other arrays are as the first call left them. */
+int rc_snapshot_decode_paths_device(rc_snapshot *s, uint64_t n, const void *d_desc, uint64_t runs,
+                                    const uint64_t *d_text_run_first, const uint64_t *d_run_close,
+                                    const uint64_t *d_stripped_len, const uint8_t *d_file_status,
+                                    const uint8_t *d_out, const uint64_t *d_path_text,
+                                    const uint64_t *d_path_off, uint8_t *d_path_bytes, uint64_t path_room,
+                                    void *hip_stream);
+
+/* The passes in the kernel timing rc_snapshot_timing_enable switches on: the summed milliseconds
+ * of the fields passes, the scans and the path passes (and their number in calls); clears them. */
+int rc_snapshot_files_timing_read(rc_snapshot *s, double *fields_ms, double *scan_ms, double *paths_ms,
+                                  uint64_t *calls);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,7 @@ RC_CIPHER_NONE, RC_CIPHER_AES_GCM, RC_CIPHER_CHACHA20_POLY1305 = 0, 1, 2
 RC_CHUNK_OK, RC_CHUNK_BAD_TAG, RC_CHUNK_CORRUPT = 0, 1, 2
 RC_TABLE_OK, RC_TABLE_BAD_TAG, RC_TABLE_NOT_CANONICAL = 0, 1, 2
 RC_PARTS_OK, RC_PARTS_NOT_CANONICAL = 0, 2
+RC_FILES_OK, RC_FILES_NOT_CANONICAL = 0, 2
 RC_PART_FIRST, RC_PART_LAST = 1, 2  # word 7 of a part record read back
 RC_SNAPSHOT_PART_WORDS = 8
 RC_SNAPSHOT_TEXT_DESC_BYTES = 32
@@ -220,6 +221,12 @@ SIGNATURES = {
     'rc_snapshot_read_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(_u64)]),
+    'rc_snapshot_path_bytes_for': (_u64, [_p, _u64]),
+    'rc_snapshot_parse_files_device': (_int, [_p, _u64, _p, _u64, _p, _p, _p, _p, _p, _u32, _p, _p, _p, _p, _p, _p, _p,
+                                              _p, _p, _p]),
+    'rc_snapshot_decode_paths_device': (_int, [_p, _u64, _p, _u64, _p, _p, _p, _p, _p, _p, _p, _p, _u64, _p]),
+    'rc_snapshot_files_timing_read': (_int, [_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),
 }
 
 

@@ -25,7 +25,7 @@ SOURCES = [os.path.join(CSRC, n) for n in ('kernels.hip', 'capi.cpp', 'blake2b.h
                                              'sha2.hip', 'sha3.hip', 'restore.hip', 'capi_restore.cpp',
                                              'index.hip', 'capi_index.cpp', 'gc.hip', 'capi_gc.cpp', 'snapshot.hip',
                                              'snapshot_write.hip', 'snapshot_data.hip', 'snapshot_text.hip',
-                                             'snapshot_parse.hip', 'capi_snapshot.cpp')]
+                                             'snapshot_parse.hip', 'snapshot_fields.hip', 'capi_snapshot.cpp')]
 HEADERS = [os.path.join(CSRC, n) for n in ('gclmul.h', 'digest_kernels.h', 'capi_internal.h', 'cipher_kernels.h',
                                              'knobs.h', 'diag.h', 'cipher_host.h', 'chacha_kernels.h',
                                              'poly1305_limbs.h', 'sha_kernels.h', 'sha_walk.h',

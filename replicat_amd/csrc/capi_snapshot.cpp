@@ -25,13 +25,14 @@ static_assert(RC_TABLE_OK == RC_CHUNK_OK && RC_TABLE_BAD_TAG == RC_CHUNK_BAD_TAG
 
 namespace {
 
-// The event pairs of a handle, one per stage (the five rc_snapshot_*timing_read).
+// The event pairs of a handle, one per stage (the six rc_snapshot_*timing_read).
 enum Timer {
     kCrypt, kDecode, kB64,         // loading (snapshot.hip)
     kEncode, kB64Encode, kSeal,    // writing (snapshot_write.hip)
     kParts, kScan, kData,          // writing `data` (snapshot_data.hip)
     kTextLen, kText,               // writing the files' text (snapshot_text.hip)
     kFind, kParse, kSums, kStrip,  // reading `data` (snapshot_parse.hip)
+    kFields, kPathScan, kPaths,    // reading the files' text (snapshot_fields.hip)
     kTimers
 };
 
@@ -889,6 +890,98 @@ int rc_snapshot_read_timing_read(rc_snapshot *s, double *find_ms, double *parse_
                                  uint64_t *find_calls) {
     return read_timers(s, {{kParse, parse_ms, nullptr}, {kSums, sums_ms, nullptr}, {kStrip, strip_ms, nullptr},
                            {kFind, find_ms, find_calls}});
+}
+
+// ----------------------------------------------------------------------- reading the files' text
+
+uint64_t rc_snapshot_path_bytes_for(const uint8_t *text, uint64_t len) {
+    if (len && !text) return kSnapReject;
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < len;) {
+        const uint32_t b = text[i];
+        if (b != '\\') {
+            if (b < 0x20u || b > 0x7Eu || b == '"') return kSnapReject;
+            ++total;
+            ++i;
+            continue;
+        }
+        uint32_t a[12] = {};
+        for (uint32_t k = 1; k < 12 && i + k < len; ++k) a[k] = text[i + k];
+        const SnapQEscape e = rc_snap_q_escape(a, len - i);
+        if (e.bytes == kSnapQBad) return kSnapReject;
+        total += e.bytes;
+        i += e.taken;
+    }
+    return total;
+}
+
+namespace {
+
+int check_files(const rc_snapshot *s, uint64_t n, const void *d_desc, uint64_t runs, const uint64_t *d_text_run_first,
+                const uint64_t *d_run_close, const uint64_t *d_stripped_len, const uint8_t *d_out, SnapFiles &a) {
+    if (!s) return rc_fail(RC_ERR_ARGUMENT, "null snapshot handle");
+    if (n > 0xFFFFFFFFull || runs > 0xFFFFFFFFull) return rc_fail(RC_ERR_ARGUMENT, "2^32 or more texts or runs");
+    if (n && (!d_desc || !d_text_run_first || !d_run_close || !d_stripped_len || !d_out))
+        return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    a = SnapFiles{static_cast<const SnapParseText *>(d_desc), n, runs, d_text_run_first, d_run_close, d_stripped_len,
+                  d_out};
+    return 0;
+}
+
+}  // namespace
+
+int rc_snapshot_parse_files_device(rc_snapshot *s, uint64_t n, const void *d_desc, uint64_t runs,
+                                   const uint64_t *d_text_run_first, const uint64_t *d_run_close,
+                                   const uint64_t *d_stripped_len, const uint8_t *d_status, const uint8_t *d_out,
+                                   uint32_t digest_size, uint8_t *d_file_status, uint8_t *d_has_metadata,
+                                   uint64_t *d_first_len, uint64_t *d_last_off, uint8_t *d_digests,
+                                   uint8_t *d_unfinished, int64_t *d_metadata, uint64_t *d_path_text,
+                                   uint64_t *d_path_off, void *hip_stream) {
+    SnapFiles a;
+    if (int rc = check_files(s, n, d_desc, runs, d_text_run_first, d_run_close, d_stripped_len, d_out, a)) return rc;
+    if (digest_size < 1 || digest_size > RC_DIGEST_SLOT)
+        return rc_fail(RC_ERR_ARGUMENT, "digest_size must be 1..64, not %u", digest_size);
+    if (n == 0) return RC_OK;
+    if (!d_status || !d_file_status || !d_has_metadata || !d_first_len || !d_last_off || !d_path_off ||
+        (runs && (!d_digests || !d_unfinished || !d_metadata || !d_path_text)))
+        return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    RC_HIP_TRY(hipMemsetAsync(d_file_status, RC_FILES_OK, n, st));
+    RC_HIP_TRY(hipMemsetAsync(d_has_metadata, 0, n, st));
+    RC_HIP_TRY(hipMemsetAsync(d_first_len, 0, n * sizeof(uint64_t), st));
+    RC_HIP_TRY(hipMemsetAsync(d_last_off, 0, n * sizeof(uint64_t), st));
+    RC_HIP_TRY(hipMemsetAsync(d_path_off, 0, (runs + 1) * sizeof(uint64_t), st));
+    if (int rc = rc::timed(s->timers[kFields], st, [&] {
+            return rc_snap_launch_file_fields(a, d_status, digest_size, d_file_status, d_has_metadata, d_first_len,
+                                              d_last_off, d_digests, d_unfinished, d_metadata, d_path_text, d_path_off,
+                                              st);
+        }))
+        return rc;
+    return rc::timed(s->timers[kPathScan], st, [&] { return rc_gc_launch_scan(d_path_off, runs, d_path_off + runs, st); });
+}
+
+int rc_snapshot_decode_paths_device(rc_snapshot *s, uint64_t n, const void *d_desc, uint64_t runs,
+                                    const uint64_t *d_text_run_first, const uint64_t *d_run_close,
+                                    const uint64_t *d_stripped_len, const uint8_t *d_file_status, const uint8_t *d_out,
+                                    const uint64_t *d_path_text, const uint64_t *d_path_off, uint8_t *d_path_bytes,
+                                    uint64_t path_room, void *hip_stream) {
+    SnapFiles a;
+    if (int rc = check_files(s, n, d_desc, runs, d_text_run_first, d_run_close, d_stripped_len, d_out, a)) return rc;
+    if (n == 0 || runs == 0) return RC_OK;
+    if (!d_file_status || !d_path_text || !d_path_off || !d_path_bytes) return rc_fail(RC_ERR_ARGUMENT, "null arrays");
+    const hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::lock_guard<std::mutex> lock(s->mu);
+    rc::DeviceGuard guard(s->device);
+    return rc::timed(s->timers[kPaths], st, [&] {
+        return rc_snap_launch_file_paths(a, d_file_status, d_path_text, d_path_off, d_path_bytes, path_room, st);
+    });
+}
+
+int rc_snapshot_files_timing_read(rc_snapshot *s, double *fields_ms, double *scan_ms, double *paths_ms,
+                                  uint64_t *calls) {
+    return read_timers(s, {{kPathScan, scan_ms, nullptr}, {kPaths, paths_ms, nullptr}, {kFields, fields_ms, calls}});
 }
 
 }  // extern "C"

@@ -39,40 +39,6 @@ constexpr uint32_t kBulkLds = kBulkSpan + 32;
 constexpr uint32_t kBulkOut = kSnapThreads * kSnapLaneBytes;
 constexpr uint32_t kBulkOutLds = kBulkOut + 16;
 
-// The value of a base64 character (standard alphabet), or a negative number.
-__device__ __forceinline__ int b64_value(uint32_t c) {
-    int v = -1;
-    if (c - 'A' < 26u) v = int(c - 'A');
-    if (c - 'a' < 26u) v = int(c - 'a') + 26;
-    if (c - '0' < 10u) v = int(c - '0') + 52;
-    if (c == '+') v = 62;
-    if (c == '/') v = 63;
-    return v;
-}
-
-// Four characters (the first in the low byte) as 24 bits, the first decoded byte on top.  The
-// last `pad` of them must be '=' and the bits of the last data character that no byte takes must
-// be zero; anything else sets bad.
-__device__ __forceinline__ uint32_t b64_group(uint32_t chars, uint32_t pad, bool &bad) {
-    uint32_t t = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) {
-        const uint32_t c = (chars >> (8 * k)) & 255u;
-        uint32_t v = 0;
-        if (k >= 4 - pad) {
-            bad |= c != '=';
-        } else {
-            const int d = b64_value(c);
-            bad |= d < 0;
-            v = uint32_t(d) & 63u;
-        }
-        t = (t << 6) | v;
-    }
-    // pad == 1: the third byte has only unused bits; pad == 2: the second and third
-    bad |= (pad >= 1 && (t & 0xFFu)) || (pad == 2 && (t & 0xFF00u));
-    return t;
-}
-
 // One atomic that makes the verdict byte at p `value` when the byte can only move one way:
 // set_bits ORs value in, otherwise the byte is cleared.
 __device__ __forceinline__ void flag_byte(uint8_t *p, uint32_t value, bool set_bits) {

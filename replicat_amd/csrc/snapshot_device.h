@@ -1,8 +1,9 @@
-// snapshot_device.h -- what the five snapshot .hip files share (snapshot.hip, snapshot_write.hip,
-// snapshot_data.hip, snapshot_text.hip, snapshot_parse.hip): the global address space and its
-// granule types, the staging of a span through LDS, the base64 characters, the workgroup scan, the
-// one binary search, and the launchers' grid size.  Device helpers are always inlined: a file that
-// uses none of them compiles as before.
+// snapshot_device.h -- what the six snapshot .hip files share (snapshot.hip, snapshot_write.hip,
+// snapshot_data.hip, snapshot_text.hip, snapshot_parse.hip, snapshot_fields.hip): the global address
+// space and its granule types, the staging of a span through LDS, the base64 characters both ways,
+// the strict reader of a text (aligned words, literals, canonical decimals), the wave and the
+// workgroup scan, the one binary search, and the launchers' grid size.  Device helpers are always
+// inlined: a file that uses none of them compiles as before.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -42,6 +43,115 @@ __device__ __forceinline__ uint32_t b64_quad(uint32_t t, uint32_t pad) {
     const uint32_t c2 = pad >= 2 ? uint32_t('=') : b64_char((t >> 6) & 63u);
     const uint32_t c3 = pad >= 1 ? uint32_t('=') : b64_char(t & 63u);
     return c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
+}
+
+// The value of a base64 character (standard alphabet), or a negative number.
+__device__ __forceinline__ int b64_value(uint32_t c) {
+    int v = -1;
+    if (c - 'A' < 26u) v = int(c - 'A');
+    if (c - 'a' < 26u) v = int(c - 'a') + 26;
+    if (c - '0' < 10u) v = int(c - '0') + 52;
+    if (c == '+') v = 62;
+    if (c == '/') v = 63;
+    return v;
+}
+
+// Four characters (the first in the low byte) as 24 bits, the first decoded byte on top.  The
+// last `pad` of them must be '=' and the bits of the last data character that no byte takes must
+// be zero; anything else sets bad.
+__device__ __forceinline__ uint32_t b64_group(uint32_t chars, uint32_t pad, bool &bad) {
+    uint32_t t = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        const uint32_t c = (chars >> (8 * k)) & 255u;
+        uint32_t v = 0;
+        if (k >= 4 - pad) {
+            bad |= c != '=';
+        } else {
+            const int d = b64_value(c);
+            bad |= d < 0;
+            v = uint32_t(d) & 63u;
+        }
+        t = (t << 6) | v;
+    }
+    // pad == 1: the third byte has only unused bits; pad == 2: the second and third
+    bad |= (pad >= 1 && (t & 0xFFu)) || (pad == 2 && (t & 0xFF00u));
+    return t;
+}
+
+// The bytes of one text, read as aligned words that each hold at least one of them; 0 past the end.
+struct TextReader {
+    uintptr_t base;
+    uint64_t len;
+    uintptr_t at = 1;  // the address of the word held (1: none)
+    uint32_t held = 0;
+    __device__ __forceinline__ uint32_t byte(uint64_t p) {
+        if (p >= len) return 0;
+        const uintptr_t a = base + p, w = a & ~uintptr_t(3);
+        if (w != at) {
+            held = *reinterpret_cast<const GLOBAL uint32_t *>(w);
+            at = w;
+        }
+        return (held >> (8 * uint32_t(a & 3))) & 255u;
+    }
+};
+
+template <int N>
+__device__ __forceinline__ bool literal(TextReader &r, uint64_t &p, const char (&s)[N]) {
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < N - 1; ++k) ok &= r.byte(p + k) == uint32_t(uint8_t(s[k]));
+    p += N - 1;
+    return ok;
+}
+
+// The digits at p, at most `most` of them (19 or fewer: their value v does not wrap): one at least,
+// no leading zero but 0 itself.
+__device__ __forceinline__ bool digits(TextReader &r, uint64_t &p, uint32_t most, uint64_t &v) {
+    const uint32_t lead = r.byte(p);
+    uint32_t nd = 0;
+    v = 0;
+    while (nd <= most) {
+        const uint32_t d = r.byte(p) - '0';
+        if (d >= 10u) break;
+        v = v * 10 + d;
+        ++nd;
+        ++p;
+    }
+    return nd >= 1 && nd <= most && !(nd > 1 && lead == '0');
+}
+
+// A canonical decimal below 2^32: one to ten digits.
+__device__ __forceinline__ bool decimal(TextReader &r, uint64_t &p, uint32_t &out) {
+    uint64_t v;
+    const bool ok = digits(r, p, 10, v);
+    out = uint32_t(v);
+    return ok && v <= 0xFFFFFFFFull;
+}
+
+// A canonical signed decimal within int64: an optional '-', one to nineteen digits, no -0.
+__device__ __forceinline__ bool decimal64(TextReader &r, uint64_t &p, int64_t &out) {
+    const bool neg = r.byte(p) == '-';
+    p += neg ? 1 : 0;
+    uint64_t v;
+    const bool ok = digits(r, p, 19, v);
+    out = int64_t(neg ? uint64_t(0) - v : v);
+    return ok && !(neg && v == 0) && v <= (uint64_t(1) << 63) - (neg ? 0u : 1u);
+}
+
+// the wave's number in its workgroup, as the scalar it is: what follows from it stays in SGPRs
+__device__ __forceinline__ uint32_t wave_index() { return uint32_t(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)); }
+
+// Exclusive prefix of v over the wave's lanes, and the sum.
+__device__ __forceinline__ uint32_t wave_scan(uint32_t v, uint32_t lane, uint32_t &total) {
+    uint32_t x = v;
+#pragma unroll
+    for (uint32_t off = 1; off < 64; off <<= 1) {
+        const uint32_t y = __shfl_up(x, off);
+        if (lane >= off) x += y;
+    }
+    total = uint32_t(__builtin_amdgcn_readlane(x, 63));
+    return x - v;
 }
 
 // Exclusive prefix of v over the workgroup's lanes, and the sum; lds holds kSnapThreads words.

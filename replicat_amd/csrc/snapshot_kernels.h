@@ -204,3 +204,84 @@ int rc_snap_launch_strip(const SnapParseText *d_texts, uint64_t n_texts, const u
                          uint64_t capacity, const uint64_t *d_run_off, const uint64_t *d_run_end,
                          const uint64_t *d_run_local, const uint64_t *d_run_group_off, const uint8_t *d_status,
                          uint8_t *d_out, uint64_t *d_run_close, uint64_t *d_stripped_len, hipStream_t st);
+
+// snapshot_fields.hip: the files' text read back from the stripped texts stage 4 leaves
+// (include/replicat_snapshot.h, "Reading the files' text").  One wave per piece, kSnapTextWaves
+// pieces per workgroup, Q kSnapTextStep bytes per wave step -- snapshot_text.hip's shape.
+constexpr uint32_t kSnapFirstMost = 4096;  // a `first` longer than this is left to the host
+constexpr uint32_t kSnapQBad = 0xFFu;
+
+// One escape of Q as the device and rc_snapshot_path_bytes_for judge it.  a[k], k = 1 .. 11, is
+// the byte k behind the backslash (anything where Q has ended) and `left` the bytes of Q from the
+// backslash on.  bytes: what it decodes to in UTF-8 ('surrogatepass'), or kSnapQBad for an escape
+// encode_basestring_ascii does not write; taken: its text, 2, 6 or -- a high surrogate with a low
+// one directly behind it, which json.loads joins -- 12; code: the code point.
+struct SnapQEscape {
+    uint32_t bytes, taken, code;
+};
+
+__host__ __device__ inline uint32_t rc_snap_hex4(const uint32_t *a, bool &bad) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t c = a[k];
+        uint32_t d = 0;
+        if (c - '0' < 10u)
+            d = c - '0';
+        else if (c - 'a' < 6u)  // lowercase only
+            d = c - 'a' + 10;
+        else
+            bad = true;
+        v = (v << 4) | d;
+    }
+    return v;
+}
+
+__host__ __device__ inline SnapQEscape rc_snap_q_escape(const uint32_t *a, uint64_t left) {
+    const SnapQEscape refused{kSnapQBad, 2, 0};
+    if (left < 2) return refused;  // a dangling backslash
+    const uint32_t c = a[1];
+    const uint32_t brief = c == '"' || c == '\\' ? c : c == 'b' ? 8u : c == 'f' ? 12u : c == 'n' ? 10u : c == 'r' ? 13u
+                                                                                                   : c == 't' ? 9u : 0u;
+    if (brief) return SnapQEscape{1, 2, brief};
+    if (c != 'u' || left < 6) return refused;
+    bool bad = false;
+    const uint32_t u = rc_snap_hex4(a + 2, bad);
+    const bool has_brief = u == 8 || u == 9 || u == 10 || u == 12 || u == 13;
+    if (bad || !((u < 0x20u && !has_brief) || u == 0x7Fu || u >= 0x80u)) return refused;
+    if (u >= 0xD800u && u < 0xDC00u && left >= 12 && a[6] == '\\' && a[7] == 'u') {
+        bool bad_low = false;  // such a low half is refused where it stands
+        const uint32_t low = rc_snap_hex4(a + 8, bad_low);
+        if (!bad_low && low >= 0xDC00u && low < 0xE000u)
+            return SnapQEscape{4, 12, 0x10000u + ((u - 0xD800u) << 10) + (low - 0xDC00u)};
+    }
+    return SnapQEscape{u < 0x80u ? 1u : u < 0x800u ? 2u : 3u, 6, u};
+}
+
+// Byte k of the UTF-8 of `code` in `bytes` bytes.
+__host__ __device__ inline uint32_t rc_snap_utf8_byte(uint32_t code, uint32_t bytes, uint32_t k) {
+    if (bytes == 1) return code;
+    const uint32_t shift = 6 * (bytes - 1 - k);
+    if (k) return 0x80u | ((code >> shift) & 0x3Fu);
+    return ((0xF00u >> bytes) & 0xFFu) | (code >> shift);  // 110xxxxx, 1110xxxx, 11110xxx
+}
+
+// What the two passes read: the texts of a call as stage 4 left them.
+struct SnapFiles {
+    const SnapParseText *texts;
+    uint64_t n_texts, runs;
+    const uint64_t *text_run_first, *run_close, *stripped_len;
+    const uint8_t *out;
+};
+
+// The fields pass: per text d_file_status (RC_FILES_OK beforehand), d_has_metadata, d_first_len,
+// d_last_off; per file the 64-byte slot, the flag, the metadata row, where Q starts in its text
+// (d_path_text) and the bytes it decodes to (d_path_len, 0 beforehand).
+int rc_snap_launch_file_fields(const SnapFiles &a, const uint8_t *d_status, uint32_t digest_bytes,
+                               uint8_t *d_file_status, uint8_t *d_has_metadata, uint64_t *d_first_len,
+                               uint64_t *d_last_off, uint8_t *d_digests, uint8_t *d_unfinished, int64_t *d_metadata,
+                               uint64_t *d_path_text, uint64_t *d_path_len, hipStream_t st);
+// The path pass: Q of every file of a text whose file status is RC_FILES_OK, decoded to
+// d_path_bytes + d_path_off[f]; no byte at or behind path_room.
+int rc_snap_launch_file_paths(const SnapFiles &a, const uint8_t *d_file_status, const uint64_t *d_path_text,
+                              const uint64_t *d_path_off, uint8_t *d_path_bytes, uint64_t path_room, hipStream_t st);

@@ -40,48 +40,6 @@ __device__ __forceinline__ uint32_t word_at(const uint32_t (&w)[12], int j) {
     return __funnelshift_r(w[j >> 2], w[(j >> 2) + 1], 8 * (j & 3));
 }
 
-// The bytes of one text, read as aligned words that each hold at least one of them; 0 past the end.
-struct TextReader {
-    uintptr_t base;
-    uint64_t len;
-    uintptr_t at = 1;  // the address of the word held (1: none)
-    uint32_t held = 0;
-    __device__ __forceinline__ uint32_t byte(uint64_t p) {
-        if (p >= len) return 0;
-        const uintptr_t a = base + p, w = a & ~uintptr_t(3);
-        if (w != at) {
-            held = *reinterpret_cast<const GLOBAL uint32_t *>(w);
-            at = w;
-        }
-        return (held >> (8 * uint32_t(a & 3))) & 255u;
-    }
-};
-
-template <int N>
-__device__ __forceinline__ bool literal(TextReader &r, uint64_t &p, const char (&s)[N]) {
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < N - 1; ++k) ok &= r.byte(p + k) == uint32_t(uint8_t(s[k]));
-    p += N - 1;
-    return ok;
-}
-
-// A canonical decimal below 2^32: one to ten digits, no leading zero but 0 itself.
-__device__ __forceinline__ bool decimal(TextReader &r, uint64_t &p, uint32_t &out) {
-    const uint32_t lead = r.byte(p);
-    uint64_t v = 0;
-    uint32_t nd = 0;
-    while (nd < 11) {
-        const uint32_t d = r.byte(p) - '0';
-        if (d >= 10u) break;
-        v = v * 10 + d;
-        ++nd;
-        ++p;
-    }
-    out = uint32_t(v);
-    return nd >= 1 && nd <= 10 && !(nd > 1 && lead == '0') && v <= 0xFFFFFFFFull;
-}
-
 }  // namespace
 
 // kScatter false: counts[0][b] = the parts that start in workgroup b's granules, counts[1][b] the

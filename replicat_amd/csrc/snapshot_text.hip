@@ -43,20 +43,6 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// the wave's number in its workgroup, as the scalar it is: what follows from it stays in SGPRs
-__device__ __forceinline__ uint32_t wave_index() { return uint32_t(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)); }
-
-__device__ __forceinline__ uint32_t wave_scan(uint32_t v, uint32_t lane, uint32_t &total) {
-    uint32_t x = v;
-#pragma unroll
-    for (uint32_t off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off);
-        if (lane >= off) x += y;
-    }
-    total = uint32_t(__builtin_amdgcn_readlane(x, 63));
-    return x - v;
-}
-
 __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
 #pragma unroll
     for (uint32_t off = 32; off; off >>= 1) v += __shfl_xor(v, off);

@@ -253,8 +253,7 @@ def plan_restore_arrays(loaded, file_regex=None, *, index=None) -> RestorePlanAr
         sizes = sp.file_size.tolist()
         mask = np.zeros(len(sizes), dtype=bool)
         base = len(paths)  # file k of this snapshot is paths[base + k]
-        for k, entry in enumerate(sp.files):
-            path = entry['path']
+        for k, path in enumerate(sp.paths):  # of a snapshot loaded with columns: no dict per file
             paths.append(path)
             if path in files or (pattern is not None and pattern.search(path) is None):
                 continue

@@ -42,13 +42,11 @@ from .chunker import _ptr_array
 from .hashing import SLOT
 from .naming import ChunkNaming, snapshot_location
 from .pipeline import ChunkEncryption
-from .snapshots import (ALIGN, _ENC_HEAD, _ENC_MID, _ENC_TAIL, _PLAIN_HEAD, _PLAIN_MID, _offsets, _SnapshotHandle,
-                        serialize, type_hint)
+from .snapshots import (ALIGN, METADATA_KEYS, _ENC_HEAD, _ENC_MID, _ENC_TAIL, _PLAIN_HEAD, _PLAIN_MID, _offsets,
+                        _SnapshotHandle, serialize, type_hint)
 
 NONCE_PREFIX = 64   # bytes of a table's text an injected nonce rule is shown
 SMALL_PIECE = 4096  # fixed parts shorter than this are placed by one scatter
-# the columns of a metadata array: read_metadata's keys, in its order (repository.py:505-519)
-METADATA_KEYS = ('st_mode', 'st_uid', 'st_gid', 'st_size', 'st_atime_ns', 'st_mtime_ns', 'st_ctime_ns')
 # the text kernel's geometry (csrc/snapshot_kernels.h): fixed pieces per workgroup, path bytes per wave step
 FILE_TEXT_PIECES_PER_GROUP = 4
 FILE_TEXT_STEP = 64

@@ -24,7 +24,11 @@ one is given.  Only ``data`` -- irregular JSON -- is deserialised on the host, a
 for.  With ``parts=True`` the one array inside ``data`` that grows with the chunks, the parts of
 every file, is read on the device too (include/replicat_snapshot.h, "Reading `data`"): ``data``
 is then a ``SnapshotParts`` -- arrays, sizes, counts and positions -- and the host's json.loads
-sees only the text that is left when the parts are taken out (``accept_stripped``).
+sees only the text that is left when the parts are taken out (``accept_stripped``).  With
+``columns=True`` as well that text is read on the device too ("Reading the files' text"): the
+files come back as a ``FileColumns`` -- path bytes and offsets, digests, the unfinished flag, the
+metadata integers -- and the host's JSON work for an accepted text is ``accept_ends`` over the
+hundred bytes around the files.
 
 The device accepts CANONICAL input only: the envelope, base64 and table text that ``serialize``
 writes.  ``json.loads`` and ``base64.standard_b64decode`` accept more (whitespace, stray
@@ -53,8 +57,9 @@ from typing import Any, Callable, Iterable, List, Optional, Tuple
 
 import numpy as np
 
-from ._lib import (RC_CIPHER_AES_GCM, RC_CIPHER_CHACHA20_POLY1305, RC_CIPHER_NONE, RC_PARTS_NOT_CANONICAL, RC_PARTS_OK,
-                   RC_TABLE_BAD_TAG, RC_TABLE_NOT_CANONICAL, RC_TABLE_OK, check, lib)
+from ._lib import (RC_CIPHER_AES_GCM, RC_CIPHER_CHACHA20_POLY1305, RC_CIPHER_NONE, RC_FILES_NOT_CANONICAL, RC_FILES_OK,
+                   RC_PARTS_NOT_CANONICAL, RC_PARTS_OK, RC_TABLE_BAD_TAG, RC_TABLE_NOT_CANONICAL, RC_TABLE_OK, check,
+                   lib)
 from .chunker import _current_device, _ptr_array
 from .cipher import DecryptionError
 from .hashing import SLOT, hasher_from_config, hashlib_from_config, state_init
@@ -177,6 +182,8 @@ class LoadedSnapshot:
         return {'chunks': [flat[i:i + width] for i in range(0, len(flat), width)], 'data': data}
 
 
+# the columns of a metadata array: read_metadata's keys, in its order (repository.py:505-519)
+METADATA_KEYS = ('st_mode', 'st_uid', 'st_gid', 'st_size', 'st_atime_ns', 'st_mtime_ns', 'st_ctime_ns')
 LIST_OPEN = b'"chunks":['  # what serialize writes in front of a file's parts, and nowhere else
 PART_MIN_LEN = 38          # rc_snapshot_part_len_for(0, 0, 0, 0): a part's text with its separator
 
@@ -200,6 +207,63 @@ def positions_of(part_first, sizes, counters) -> np.ndarray:
     return position
 
 
+@dataclass
+class FileColumns:
+    """The files of one snapshot as columns, in listing order: ``SnapshotLayout``'s columnar form
+    (snapshot_write.py), so what a snapshot loaded can be handed to the writer.  Path k is the
+    bytes ``path_off[k] .. path_off[k + 1] - 1`` of ``path_bytes``, what
+    ``str.encode('utf-8', 'surrogatepass')`` gives; ``digests`` is (m, L) uint8, zero for a file
+    flagged ``unfinished`` (whose digest and metadata are null); ``metadata`` is (m, 7) int64 with
+    the columns ``METADATA_KEYS``, or None when the files have no such key."""
+    path_bytes: np.ndarray
+    path_off: np.ndarray
+    digests: np.ndarray
+    unfinished: np.ndarray
+    metadata: Optional[np.ndarray] = None
+
+    @property
+    def m(self) -> int:
+        return int(self.path_off.size) - 1
+
+    def path(self, k: int) -> str:
+        a, b = int(self.path_off[k]), int(self.path_off[k + 1])
+        return self.path_bytes[a:b].tobytes().decode('utf-8', 'surrogatepass')
+
+    def paths(self) -> List[str]:
+        flat, off = self.path_bytes.tobytes(), self.path_off.tolist()
+        return [flat[a:b].decode('utf-8', 'surrogatepass') for a, b in zip(off[:-1], off[1:])]
+
+    def entries(self) -> list:
+        """The reference's per-file dicts with ``chunks`` emptied."""
+        flat, width = self.digests.tobytes(), self.digests.shape[1]
+        open_ = self.unfinished.tolist()
+        rows = self.metadata.tolist() if self.metadata is not None else None
+        out = []
+        for k, path in enumerate(self.paths()):
+            entry = {'path': path, 'chunks': [], 'digest': None if open_[k] else flat[k * width:(k + 1) * width]}
+            if rows is not None:
+                entry['metadata'] = None if open_[k] else dict(zip(METADATA_KEYS, rows[k]))
+            out.append(entry)
+        return out
+
+
+def accept_ends(first: bytes, last: bytes) -> Optional[dict]:
+    """The whole of the host's JSON work for a text whose files the device read: ``first`` is the
+    text up to the ``[`` of ``files``, ``last`` what follows its ``]``.  Returns
+    ``deserialize(first + b']' + last)`` when that is a dict with ``files == []`` and ``serialize``
+    of it is those bytes again, else None."""
+    text = bytes(first) + b']' + bytes(last)
+    try:
+        data = deserialize(text)
+        if not isinstance(data, dict) or type(data.get('files')) is not list or data['files']:
+            return None
+        if serialize(data) != text:
+            return None
+    except Exception:  # whatever json, base64 or the recursion limit raise: the reference's path decides
+        return None
+    return data
+
+
 class SnapshotParts:
     """A snapshot's ``data`` with the parts of its files as arrays instead of one dict per part.
 
@@ -210,18 +274,33 @@ class SnapshotParts:
     ``file_chunks[k]`` are what ``list-files`` prints, ``size`` what ``list-snapshots`` prints,
     ``sorted`` says that every file listed its parts by strictly increasing counter.  A dict the
     device did not read (``from_dict``) that does not fit the arrays -- a part that is no dict
-    of three integers below 2^32 -- has ``part_first`` None and only ``to_dict()``."""
+    of three integers below 2^32 -- has ``part_first`` None and only ``to_dict()``.
+
+    ``columns`` is the ``FileColumns`` of a snapshot whose per-file text the device read
+    (``load(parts=True, columns=True)``), None when the host read it; ``files`` is then built
+    from ``columns.entries()`` on first access, and ``paths`` builds no dict at all."""
 
     def __init__(self, data, part_first, start, end, index, counter, position, file_size, file_chunks, size,
-                 sorted, raw=None):
-        self._data, self._raw = data, raw
+                 sorted, raw=None, columns=None):
+        self._data, self._raw, self.columns, self._files = data, raw, columns, None
         self.part_first, self.start, self.end, self.index, self.counter = part_first, start, end, index, counter
         self.position, self.file_size, self.file_chunks = position, file_size, file_chunks
         self.size, self.sorted = size, sorted
 
     @property
     def files(self) -> list:
-        return self._data['files']
+        if self.columns is None:
+            return self._data['files']
+        if self._files is None:
+            self._files = self.columns.entries()
+        return self._files
+
+    @property
+    def paths(self) -> List[str]:
+        """The path of every file, in listing order."""
+        if self.columns is None:
+            return [entry['path'] for entry in self._data['files']]
+        return self.columns.paths()
 
     @property
     def utc_timestamp(self):
@@ -246,7 +325,7 @@ class SnapshotParts:
         first = self.part_first.tolist()
         cols = [a.tolist() for a in (self.start, self.end, self.index, self.counter)]
         files = []
-        for k, entry in enumerate(self._data['files']):
+        for k, entry in enumerate(self.files):
             entry = dict(entry)
             entry['chunks'] = [{'range': [cols[0][p], cols[1][p]], 'index': cols[2][p], 'counter': cols[3][p]}
                                for p in range(first[k], first[k + 1])]
@@ -342,6 +421,13 @@ class TextParts:
     run: Optional[np.ndarray] = None            # the list of every part, counted from the text's first
     offset: Optional[np.ndarray] = None         # of the part's text in the text
     flags: Optional[np.ndarray] = None          # RC_PART_FIRST, RC_PART_LAST
+    # with files=True: ``stripped`` is None where the device read the files (files_status
+    # RC_FILES_OK and at least one file) and the host accepted what is around them
+    files_status: Optional[int] = None
+    columns: Optional[FileColumns] = None
+    first: Optional[bytes] = None               # the text up to the '[' of files
+    last: Optional[bytes] = None                # the text behind its ']'
+    ends: Optional[dict] = field(default=None, repr=False)  # accept_ends(first, last)
 
 
 class _Buffers:
@@ -484,7 +570,7 @@ class GpuSnapshotLoader(_SnapshotHandle):
     field is hashed on host threads."""
     _THREAD_PREFIX = 'snapshot-data-digest'
     _STATS = ('snapshots', 'host_fallbacks', 'data_digests_host', 'data_digests_device', 'bytes_uploaded',
-              'bytes_copied_back', 'data_bytes_copied_back')
+              'bytes_copied_back', 'data_bytes_copied_back', 'file_text_on_host')
 
     def __init__(self, *, encryption: Optional[ChunkEncryption], userkey: Optional[bytes] = None,
                  hashing='blake2b', digest_size=None, hash_bits=None, batch_bytes=DEFAULT_BATCH,
@@ -563,7 +649,7 @@ class GpuSnapshotLoader(_SnapshotHandle):
     # --------------------------------------------------------------------------- load
 
     def load(self, items, *, into=None, select: Optional[Callable[[str], bool]] = None,
-             want_chunks=True, want_data=True, parts=False) -> List[LoadedSnapshot]:
+             want_chunks=True, want_data=True, parts=False, columns=False) -> List[LoadedSnapshot]:
         """Load ``(path, contents)`` pairs: the location and the file bytes as downloaded or read
         from the cache.  With ``into`` (a ``GpuChunkGC``), the digests of every loaded snapshot
         for which ``select(path)`` is true (all, when ``select`` is None) are added to the
@@ -575,8 +661,18 @@ class GpuSnapshotLoader(_SnapshotHandle):
         arrays are copied back, and ``stats['data_bytes_copied_back']`` counts that text.  A
         ``data`` the device does not accept (``accept_stripped``) is deserialised on the host as
         before, counts in ``stats['host_fallbacks']`` and gives the same object.
+        With ``columns`` (which needs ``parts``: ValueError without) the text without the parts
+        is read on the device as well: a text it accepts comes back as a ``FileColumns``
+        (``SnapshotParts.columns``) with only the bytes before the first file and behind the last,
+        which ``accept_ends`` judges; ``stats['data_bytes_copied_back']`` counts exactly those
+        bytes, or the stripped text of a snapshot the device did not accept or that has no file,
+        which takes ``accept_stripped`` as before and counts in ``stats['file_text_on_host']``.
+        This costs at most one synchronisation more per batch than ``parts`` alone, because the
+        total of the decoded paths sizes a copy.
         The result is in the order of ``items``."""
         self._live()
+        if columns and not parts:
+            raise ValueError('columns=True reads the text that parts=True leaves: pass both')
         items = [(path, bytes(contents)) for path, contents in items]
         out: List[Optional[LoadedSnapshot]] = [None] * len(items)
         split = split_encrypted if self.encrypted else split_plain
@@ -586,7 +682,7 @@ class GpuSnapshotLoader(_SnapshotHandle):
         def flush():
             nonlocal batch, size
             if batch:
-                run(batch, out, into, select, want_chunks, want_data, bool(parts and want_data))
+                run(batch, out, into, select, want_chunks, want_data, bool(parts and want_data), bool(columns))
             batch, size = [], 0
 
         for pos, (path, contents) in enumerate(items):
@@ -646,12 +742,16 @@ class GpuSnapshotLoader(_SnapshotHandle):
         return self._read_timers('rc_snapshot_read_timing_read', ('find_ms', 'parse_ms', 'sums_ms', 'strip_ms'),
                                  'find_calls')
 
-    def _parts_begin(self, ptrs, lens, full=False):
+    def files_timing_read(self) -> dict:
+        """Summed kernel milliseconds of the passes that read the files' text since the last read."""
+        return self._read_timers('rc_snapshot_files_timing_read', ('fields_ms', 'scan_ms', 'paths_ms'), 'files_calls')
+
+    def _parts_begin(self, ptrs, lens, full=False, files=False):
         """Enqueue the four stages over the device texts ``ptrs[i]`` of ``lens[i]`` bytes on the
         loader's stream (which the caller has made current) and the copy of what the host needs to
         size the rest.  ``_parts_finish``, after a synchronisation, fetches the arrays."""
         torch, L = self._torch, lib()
-        job = SimpleNamespace(n=len(lens), lens=[int(x) for x in lens], full=full)
+        job = SimpleNamespace(n=len(lens), lens=[int(x) for x in lens], full=full, files=files)
         n = job.n
         cap = job.cap = sum(parts_room(ln) for ln in job.lens)
         job.out_off, total = _offsets(job.lens)
@@ -716,7 +816,9 @@ class GpuSnapshotLoader(_SnapshotHandle):
     def _parts_finish(self, job) -> List[TextParts]:
         """After the synchronisation behind ``_parts_begin``: copy back the stripped texts, the
         arrays per run and the arrays per part -- nothing else -- and cut them per text.  One
-        synchronisation (two when a run has to be sorted)."""
+        synchronisation (two when a run has to be sorted).  A job begun with ``files`` first
+        enqueues the two passes over the files' text and waits once more for what they say per
+        text; of a text they accept only ``first`` and ``last`` come back, with the columns."""
         torch = self._torch
         n, cap, W = job.n, job.cap, 8
         small = job.h_small.numpy()
@@ -730,6 +832,8 @@ class GpuSnapshotLoader(_SnapshotHandle):
         total, runs = min(int(tf[n]), cap), min(int(rf[n]), cap)
         good = [i for i in range(n) if status[i] == RC_PARTS_OK]
         words = 8 if job.full else 4
+        fj = self._files_begin(job, runs, status, rf, slen) if job.files else None
+        host_text = good if fj is None else [i for i in good if not fj.device[i]]
         with torch.cuda.stream(self._stream):
             if not all_sorted and total:
                 self._parts_resort(job, total)
@@ -739,7 +843,7 @@ class GpuSnapshotLoader(_SnapshotHandle):
             cols = (rec if job.full else rec[:, 1:5]).t().contiguous()  # one row per field
             part_bytes = 4 * words * total + W * total
             run_bytes = W * (runs + 1) + 3 * W * runs + runs
-            text_bytes = sum(int(slen[i]) for i in good)
+            text_bytes = sum(int(slen[i]) for i in host_text)
             h_parts = self._buf.get('p_h_parts', max(part_bytes, ALIGN), pinned=True)
             h_runs = self._buf.get('p_h_runs', max(_up(run_bytes) + 4 * ALIGN, ALIGN), pinned=True)
             h_out = self._buf.get('p_h_out', max(text_bytes, ALIGN), pinned=True)
@@ -752,12 +856,14 @@ class GpuSnapshotLoader(_SnapshotHandle):
                 if nbytes:
                     h_runs[a:a + nbytes].copy_(t[:nbytes], non_blocking=True)
             text_at, o = {}, 0
-            for i in good:
+            for i in host_text:
                 text_at[i] = o
                 if slen[i]:
                     h_out[o:o + int(slen[i])].copy_(job.out[job.out_off[i]:job.out_off[i] + int(slen[i])],
                                                     non_blocking=True)
                 o += int(slen[i])
+            if fj is not None:
+                self._files_copy(job, fj, slen)
             self._stream.synchronize()
         self.stats['bytes_copied_back'] += part_bytes + run_bytes + text_bytes
         self.stats['data_bytes_copied_back'] += text_bytes
@@ -777,7 +883,8 @@ class GpuSnapshotLoader(_SnapshotHandle):
             if tp.status != RC_PARTS_OK:
                 continue
             a, b, ra, rb = int(tf[i]), int(tf[i + 1]), int(rf[i]), int(rf[i + 1])
-            tp.stripped = out_np[text_at[i]:text_at[i] + int(slen[i])].tobytes()
+            if i in text_at:
+                tp.stripped = out_np[text_at[i]:text_at[i] + int(slen[i])].tobytes()
             tp.part_first = np.concatenate([rpf[ra:rb], [b]]).astype(np.uint64) - np.uint64(a)
             tp.run_close, tp.run_count, tp.run_size = rclose[ra:rb].copy(), rcount[ra:rb].copy(), rsize[ra:rb].copy()
             tp.run_sorted = rsorted[ra:rb].astype(bool)
@@ -789,17 +896,126 @@ class GpuSnapshotLoader(_SnapshotHandle):
                 tp.run = (cols[0, a:b].astype(np.int64) - ra).astype(np.int64)
                 tp.offset = cols[5, a:b].astype(np.uint64) | (cols[6, a:b].astype(np.uint64) << np.uint64(32))
                 tp.flags = cols[7, a:b].copy()
+        if fj is not None:
+            self._files_finish(job, fj, result, rf, slen)
         return result
 
-    def parse_device(self, ptrs, lens, full=True) -> List[TextParts]:
+    def _files_begin(self, job, runs, status, rf, slen):
+        """Enqueue the fields pass, the scan and the path pass over the stripped texts of ``job``
+        and wait for the words per text and the total of the paths.  ``device[i]`` says that the
+        device read the files of text i."""
+        torch, n, W = self._torch, job.n, 8
+        fj = SimpleNamespace(runs=runs)
+
+        def room(name, nbytes):
+            t = self._buf.get('f_' + name, max(nbytes, ALIGN))
+            setattr(fj, name, t)
+            return t.data_ptr()
+
+        ptr = lambda t: t.data_ptr()
+        out_room = job.out_off[-1] + _up(job.lens[-1])
+        with torch.cuda.stream(self._stream):
+            fstatus, hasmeta = room('fstatus', n), room('hasmeta', n)
+            flen, loff = room('flen', W * n), room('loff', W * n)
+            dig, unf, meta = room('dig', SLOT * runs), room('unf', runs), room('meta', 7 * W * runs)
+            ptext, poff, pbytes = room('ptext', W * runs), room('poff', W * (runs + 1)), room('pbytes', out_room)
+            stream = self._stream.cuda_stream
+            check(lib().rc_snapshot_parse_files_device(
+                self._h, n, ptr(job.desc), runs, ptr(job.rf), ptr(job.rclose), ptr(job.slen), ptr(job.status),
+                ptr(job.out), self.digest_size, fstatus, hasmeta, flen, loff, dig, unf, meta, ptext, poff, stream))
+            check(lib().rc_snapshot_decode_paths_device(
+                self._h, n, ptr(job.desc), runs, ptr(job.rf), ptr(job.rclose), ptr(job.slen), fstatus, ptr(job.out),
+                ptext, poff, pbytes, out_room, stream))
+            # file status[n] | has metadata[n] | first_len[n] | last_off[n] | the total of the paths
+            at = fj.small_at = np.cumsum([0, _up(n), _up(n), W * n, W * n, W]).tolist()
+            h = fj.h_small = self._buf.get('f_h_small', at[-1], pinned=True)
+            for a, t, nbytes in zip(at, (fj.fstatus, fj.hasmeta, fj.flen, fj.loff), (n, n, W * n, W * n)):
+                h[a:a + nbytes].copy_(t[:nbytes], non_blocking=True)
+            h[at[4]:at[5]].copy_(fj.poff[W * runs:W * (runs + 1)], non_blocking=True)
+            self._stream.synchronize()
+        self.stats['bytes_copied_back'] += 2 * n + 2 * W * n + W
+        small = h.numpy()
+        fj.status = small[at[0]:at[0] + n].copy()
+        fj.has_meta = small[at[1]:at[1] + n].astype(bool)
+        fj.first_len = small[at[2]:at[3]].view(np.uint64).astype(np.int64)
+        fj.last_off = small[at[3]:at[4]].view(np.uint64).astype(np.int64)
+        fj.path_total = min(int(small[at[4]:at[5]].view(np.uint64)[0]), out_room)
+        fj.device = [bool(status[i] == RC_PARTS_OK and fj.status[i] == RC_FILES_OK and rf[i + 1] > rf[i]
+                          and 0 < fj.first_len[i] <= fj.last_off[i] <= slen[i]) for i in range(n)]
+        return fj
+
+    def _files_copy(self, job, fj, slen):
+        """Enqueue the copies of the columns of all files of the call, and of ``first`` and ``last``
+        of every text whose files the device read."""
+        torch, W, runs, L = self._torch, 8, fj.runs, self.digest_size
+        sizes = [L * runs, runs, 7 * W * runs, W * (runs + 1), fj.path_total]
+        at = fj.col_at = np.cumsum([0] + [_up(x) for x in sizes]).tolist()
+        h = fj.h_cols = self._buf.get('f_h_cols', max(at[-1], ALIGN), pinned=True)
+        if runs:
+            digests = fj.dig[:SLOT * runs].view(runs, SLOT)[:, :L].contiguous().view(-1)
+            for a, t, nbytes in zip(at, (digests, fj.unf, fj.meta, fj.poff, fj.pbytes), sizes):
+                if nbytes:
+                    h[a:a + nbytes].copy_(t[:nbytes], non_blocking=True)
+        ends, o = {}, 0
+        for i in range(job.n):
+            if not fj.device[i]:
+                continue
+            a, b = int(fj.first_len[i]), int(fj.last_off[i])
+            ends[i] = (o, a, int(slen[i]) - b)
+            o += a + int(slen[i]) - b
+        fj.ends = ends
+        h_ends = fj.h_ends = self._buf.get('f_h_ends', max(o, ALIGN), pinned=True)
+        for i, (o_i, a, c) in ends.items():
+            base = job.out_off[i]
+            h_ends[o_i:o_i + a].copy_(job.out[base:base + a], non_blocking=True)
+            if c:
+                b = int(fj.last_off[i])
+                h_ends[o_i + a:o_i + a + c].copy_(job.out[base + b:base + b + c], non_blocking=True)
+        self.stats['bytes_copied_back'] += sum(sizes) + o
+        self.stats['data_bytes_copied_back'] += o
+
+    def _files_finish(self, job, fj, result, rf, slen):
+        """Cut the columns per text and judge ``first`` and ``last``; a text whose ends the host
+        does not accept gets its stripped text after all."""
+        W, runs, L = 8, fj.runs, self.digest_size
+        cols, at = fj.h_cols.numpy(), fj.col_at
+        digests = cols[at[0]:at[0] + L * runs].reshape(runs, L)
+        unfinished = cols[at[1]:at[1] + runs].astype(bool)
+        metadata = cols[at[2]:at[2] + 7 * W * runs].view(np.int64).reshape(runs, 7)
+        path_off = cols[at[3]:at[3] + W * (runs + 1)].view(np.uint64)
+        path_bytes = cols[at[4]:at[4] + fj.path_total]
+        ends_np = fj.h_ends.numpy()
+        for i, tp in enumerate(result):
+            if tp.status != RC_PARTS_OK:
+                continue
+            tp.files_status = int(fj.status[i])
+            if not fj.device[i]:
+                continue
+            o, a, c = fj.ends[i]
+            tp.first, tp.last = ends_np[o:o + a].tobytes(), ends_np[o + a:o + a + c].tobytes()
+            tp.ends = accept_ends(tp.first, tp.last)
+            if tp.ends is None:  # what is around the files is not what serialize writes
+                base = job.out_off[i]
+                tp.stripped = job.out[base:base + int(slen[i])].cpu().numpy().tobytes()
+                self.stats['bytes_copied_back'] += int(slen[i])
+                self.stats['data_bytes_copied_back'] += int(slen[i])
+                continue
+            ra, rb = int(rf[i]), int(rf[i + 1])
+            pa, pb = int(path_off[ra]), int(path_off[rb])
+            tp.columns = FileColumns(path_bytes[pa:pb].copy(), path_off[ra:rb + 1] - path_off[ra],
+                                     digests[ra:rb].copy(), unfinished[ra:rb].copy(),
+                                     metadata[ra:rb].copy() if fj.has_meta[i] else None)
+
+    def parse_device(self, ptrs, lens, full=True, files=False) -> List[TextParts]:
         """Read the parts of n texts that lie in device memory (``ptrs[i]``, ``lens[i]`` bytes, any
         alignment), in one call: what ``load(parts=True)`` runs on every ``data``, for tests and
-        probes."""
+        probes.  With ``files`` the files' text is read there too, as ``load(columns=True)`` does:
+        the ``TextParts`` also carry ``files_status``, ``columns``, ``first`` and ``last``."""
         self._live()
         if not len(lens):
             return []
         with self._torch.cuda.stream(self._stream):
-            job = self._parts_begin(ptrs, lens, full)
+            job = self._parts_begin(ptrs, lens, full, files)
             self._stream.synchronize()
         return self._parts_finish(job)
 
@@ -809,6 +1025,11 @@ class GpuSnapshotLoader(_SnapshotHandle):
         snapshot has to take the host's ``deserialize``."""
         if tp.status != RC_PARTS_OK:
             return None
+        if tp.columns is not None:  # file k's parts are run k's: the device proved every list a file's
+            chunks, size = tp.run_count.astype(np.uint64), tp.run_size.astype(np.uint64)
+            part_first = np.concatenate([[0], np.cumsum(chunks)]).astype(np.uint64)
+            return SnapshotParts(tp.ends, part_first, tp.start, tp.end, tp.index, tp.counter, tp.position, size, chunks,
+                                 tp.size, bool(tp.run_sorted.all()), columns=tp.columns)
         accepted = accept_stripped(tp.stripped, tp.run_close)
         if accepted is None:
             return None
@@ -859,7 +1080,7 @@ class GpuSnapshotLoader(_SnapshotHandle):
         self.stats['host_fallbacks'] += 1
         return data
 
-    def _run_plain(self, batch, out, into, select, want_chunks, want_data, parts=False):
+    def _run_plain(self, batch, out, into, select, want_chunks, want_data, parts=False, columns=False):
         torch, L = self._torch, self.digest_size
         # D first: a body whose D is not one JSON value is not of the expected shape (with parts
         # the deserialize of the stripped text says so, after the device has read D)
@@ -904,7 +1125,7 @@ class GpuSnapshotLoader(_SnapshotHandle):
             job = None
             if parts:
                 job = self._parts_begin([d_up.data_ptr() + o for o in d_offs],
-                                        [batch[b][3][3] - batch[b][3][2] for b in keep])
+                                        [batch[b][3][3] - batch[b][3][2] for b in keep], files=columns)
             h_status[:n].copy_(d_status[:n], non_blocking=True)
             slots_np = self._slots_back(d_slots, slots, want_chunks)
             self._stream.synchronize()
@@ -915,6 +1136,8 @@ class GpuSnapshotLoader(_SnapshotHandle):
                 b = keep[k]
                 pos, path, contents, (_, _, d0, d1) = batch[b]
                 datas[b] = self.parts_of(tp)
+                if columns and (datas[b] is None or datas[b].columns is None):
+                    self.stats['file_text_on_host'] += 1
                 if datas[b] is None:
                     try:
                         datas[b] = self._data_on_host(contents[d0:d1])
@@ -929,7 +1152,7 @@ class GpuSnapshotLoader(_SnapshotHandle):
         self._finish_tables(batch, k_of, counts, firsts, h_status.numpy()[:n], d_slots, slots_np, plain_of, out,
                             into, select, want_chunks, lambda k: datas[keep[k]])
 
-    def _run_encrypted(self, batch, out, into, select, want_chunks, want_data, parts=False):
+    def _run_encrypted(self, batch, out, into, select, want_chunks, want_data, parts=False, columns=False):
         torch, L, over = self._torch, self.digest_size, self.overhead
         decrypt_data = bool(want_data and self.userkey is not None)
         dev_items, host_items = [], []  # (batch position, decoded X length, decoded Y length[, decoded Y])
@@ -1041,7 +1264,7 @@ class GpuSnapshotLoader(_SnapshotHandle):
                 self.cipher.decrypt_device(ins, [it[2] for it in order], [d_key.data_ptr()] * n,
                                            [d_data.data_ptr() + o for o in q_off], flags_ptr + 2 * n + m, stream)
                 if parts:  # read where it lies; a text whose tag failed is read too, and not used
-                    job = self._parts_begin([d_data.data_ptr() + o for o in q_off], data_lens)
+                    job = self._parts_begin([d_data.data_ptr() + o for o in q_off], data_lens, files=columns)
                 elif q:
                     h_data = self._buf.get('h_data', q, pinned=True)
                     h_data[:q].copy_(d_data[:q], non_blocking=True)
@@ -1075,6 +1298,8 @@ class GpuSnapshotLoader(_SnapshotHandle):
             o = q_off[k]
             if read is not None:
                 data = self.parts_of(read[k])
+                if columns and (data is None or data.columns is None):
+                    self.stats['file_text_on_host'] += 1
                 if data is None:  # not what the device reads: the plaintext comes back after all
                     text = d_data[o:o + data_lens[k]].cpu().numpy().tobytes()
                     self.stats['bytes_copied_back'] += data_lens[k]
@@ -1088,6 +1313,7 @@ class GpuSnapshotLoader(_SnapshotHandle):
 
 
 __all__ = ['GpuSnapshotLoader', 'LoadedSnapshot', 'SnapshotParts', 'TextParts', 'accept_stripped', 'positions_of',
-           'parts_room', 'serialize', 'type_hint', 'RC_PARTS_OK', 'RC_PARTS_NOT_CANONICAL',
+           'parts_room', 'serialize', 'type_hint', 'RC_PARTS_OK', 'RC_PARTS_NOT_CANONICAL', 'FileColumns', 'accept_ends',
+           'METADATA_KEYS', 'RC_FILES_OK', 'RC_FILES_NOT_CANONICAL',
            'split_encrypted', 'split_plain', 'deserialize', 'type_reverse',
            'DecryptionError', 'ChunkEncryption', 'RC_TABLE_OK', 'RC_TABLE_BAD_TAG', 'RC_TABLE_NOT_CANONICAL']
